@@ -2,22 +2,39 @@
 """bench.py — fp32 SGEMM (M=N=K=4096) on MI355X via libtensorium_hip.so, plus
 YOLOv3-416 conv-forward images/s, per BASELINE.json's metric.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N ... bench.py --gpus N      (one process per GPU)
 
 A "step" is one pass of the hot path over one batch of synthetic input: one
 NN SGEMM 4096^3 (alpha=1, beta=0; BASELINE configs[1]) on operands already
 resident in HBM.  With N GPUs every rank runs its own independent GEMM per
 step (independent units, no data-path collective — SURVEY §8e), so scaling is
-weak and `value` = total FLOP of all ranks / max-over-ranks time.  The
-headline is timed after the secondary workloads below, at the clock the chip
-holds under sustained load (a cold GPU ramps over its first ~20 launches).
+weak and `value` = total FLOP of all ranks / max-over-ranks time.
 
-Extra fields on the single JSON line:
+A plain run does only what the headline needs: it generates the operands,
+runs W untimed and K timed steps, writes the outputs when asked to and prints
+the JSON line (`ms_per_step` = wall time of the K timed steps / K).  A cold
+GPU ramps its clock over its first ~20 launches, so set-up ends with 30
+launches of the step, counted neither as warm-up nor as timed steps.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+left in C as DIR/sgemm_C_rank<r>.npy (float32), one file per rank.  The
+operands come from fixed seeds, so two builds run with the same arguments
+can be compared file for file.  A C above the size budget (4096^2 floats are
+64 MiB) is written as a fixed, seeded sample of its rows, in ascending order.
+
+--full adds the secondary workloads and baselines below, each a run of its
+own, as extra fields on the line (null in a plain run).  They run before the
+headline, which is then timed at the clock the chip holds under sustained
+load.
+
+Fields on the single JSON line:
   roofline     — dominant kernel (sgemm_mfma) vs the fp32 MFMA peak, its
                  duration taken live with HIP events on the stream the kernel
-                 is launched on; `traffic` from the committed PMC pass
-                 (profiles/, FETCH_SIZE doubled per the gfx950 guide) or null.
+                 is launched on, around each timed step; `traffic` from the
+                 committed PMC pass (profiles/, FETCH_SIZE doubled per the
+                 gfx950 guide) or null.
+ With --full:
   cpu_baseline — the oracle's restated sgemm_nn (reference: ntensors.pas
                  cblas_sgemm -> sgemm_nn -> saxpy_avx2) on the host cores, rank
                  0 at N=1 only, on a bounded sample of rows of the same product.
@@ -56,6 +73,11 @@ def parse():
                     help="untimed steps; the GPU clock ramps over the first ~20 launches "
                          "(profiles/r01_clock_ramp.json)")
     ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary workloads, the per-kernel rooflines and the "
+                         "CPU baselines (the --no-* and --yolo-steps options trim these)")
     ap.add_argument("--yolo-steps", type=int, default=5)
     ap.add_argument("--no-yolo", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
@@ -187,6 +209,11 @@ def synthetic(torch, shape, seed, lo=-1.0, hi=1.0):
     return torch.rand(shape, generator=g, device="cuda", dtype=torch.float32) * (hi - lo) + lo
 
 
+# A cold GPU takes 1.88 ms for its first 4096^3 launch, then 1.21 -> 1.03 ms
+# over the next ~20 (profiles/r01_clock_ramp.json)
+CLOCK_RAMP_LAUNCHES = 30
+
+
 def bench_sgemm(torch, hip, ctx, rank, n, steps, warmup):
     A = synthetic(torch, (n, n), 2 * 1000 + rank)
     B = synthetic(torch, (n, n), 2 * 1000 + 500 + rank)
@@ -195,6 +222,10 @@ def bench_sgemm(torch, hip, ctx, rank, n, steps, warmup):
     def step():
         hip.gemm(False, False, n, n, n, 1.0, A, 0, n, B, 0, n, 0.0, Cm, 0, n)
 
+    # set-up: bring the chip to the clock it holds under load, whatever
+    # --warmup is (a plain run has no secondary workload in front of it)
+    for _ in range(CLOCK_RAMP_LAUNCHES):
+        step()
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -214,7 +245,24 @@ def bench_sgemm(torch, hip, ctx, rank, n, steps, warmup):
     t1 = time.perf_counter()
     wall = t1 - t0
     kern_ms = [a.elapsed_time(b) for a, b in ev]
-    return wall, float(np.mean(kern_ms)), float(np.min(kern_ms))
+    return wall, float(np.mean(kern_ms)), float(np.min(kern_ms)), Cm
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # all ranks' files together (the limit is 64 MB)
+
+
+def dump_outputs(torch, out_dir, rank, world, Cm):
+    """C as the last timed step left it -> out_dir/sgemm_C_rank<r>.npy.  Whole
+    when it fits this rank's share of the budget, else a seeded sample of its
+    rows (the same rows on every run and every rank, ascending)."""
+    n_rows, n_cols = Cm.shape
+    keep = min(n_rows, max(1, DUMP_BUDGET_BYTES // world // (4 * n_cols)))
+    if keep < n_rows:
+        rows = np.sort(np.random.default_rng(20).choice(n_rows, size=keep, replace=False))
+        Cm = Cm[torch.from_numpy(rows).to(Cm.device)]
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / f"sgemm_C_rank{rank}.npy", Cm.cpu().numpy().astype(np.float32, copy=False))
 
 
 def bench_yolo(torch, hip, ctx, rank, steps, warmup=4):
@@ -840,13 +888,15 @@ def main():
     hip = TNNHip(ctx.gpu)
     n = args.size
 
-    # The secondary workloads run first and the headline SGEMM last, so that
-    # its K timed steps run at the clock the chip holds under sustained load:
-    # a cold GPU ramps over its first ~20 launches (4096^3: 1.88 ms, then
-    # 1.21 -> 1.0 ms; profiles/r01_clock_ramp.json), which a short warm-up
-    # alone would leave inside the timed region.
+    # With --full the secondary workloads run first and the headline SGEMM
+    # last, so that its K timed steps run at the clock the chip holds under
+    # sustained load: a cold GPU ramps over its first ~20 launches (4096^3:
+    # 1.88 ms, then 1.21 -> 1.0 ms; profiles/r01_clock_ramp.json), which a
+    # short warm-up alone would leave inside the timed region.
+    with_yolo = args.full and not args.no_yolo
+    with_cpu = args.full and not args.no_cpu and rank == 0 and world == 1
     yolo = None
-    if not args.no_yolo and args.yolo_steps > 0:
+    if with_yolo and args.yolo_steps > 0:
         y = bench_yolo(torch, hip, ctx, rank, args.yolo_steps)
         ms = ctx.max(y["ms_per_batch"])
         y["ms_per_batch"] = ms
@@ -854,40 +904,43 @@ def main():
         yolo = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in y.items()}
 
     yolo_net = None
-    if not args.no_yolo and args.yolo_steps > 0:
+    if with_yolo and args.yolo_steps > 0:
         yolo_net = bench_yolo_network(torch, hip, ctx, args.yolo_steps)
     conv_bwd = None
-    if not args.no_yolo and args.yolo_steps > 0:
+    if with_yolo and args.yolo_steps > 0:
         conv_bwd = bench_conv_backward(torch, hip, ctx, rank)
     train_bwd = None
-    if not args.no_yolo and args.yolo_steps > 0:
+    if with_yolo and args.yolo_steps > 0:
         train_bwd = bench_train_backward(torch, hip, ctx)
-    ew = None if args.no_yolo else bench_elementwise_roofline(torch, hip)
+    ew = bench_elementwise_roofline(torch, hip) if with_yolo else None
     yolo_dp = None
-    if not args.no_yolo and args.yolo_steps > 0:
+    if with_yolo and args.yolo_steps > 0:
         yolo_dp = bench_yolo_dp(torch, hip, ctx, args.yolo_steps)
-    mnist = None if args.no_mnist else bench_mnist(torch, hip, ctx)
+    mnist = bench_mnist(torch, hip, ctx) if args.full and not args.no_mnist else None
     # (the MFMA-bound config 4 right before the headline: the clock settles
     # under MFMA load, not under the latency-bound train step)
-    batched = None if args.no_batched else bench_batched(torch, hip, ctx)
+    batched = bench_batched(torch, hip, ctx) if args.full and not args.no_batched else None
 
-    wall, kern_ms, kern_min = bench_sgemm(torch, hip, ctx, rank, n, args.steps, args.warmup)
+    wall, kern_ms, kern_min, Cm = bench_sgemm(torch, hip, ctx, rank, n, args.steps, args.warmup)
     wall = ctx.max(wall)
     flop = 2.0 * n * n * n
     ms_per_step = wall / args.steps * 1e3
     value = world * flop / (ms_per_step / 1e3) / 1e9   # GFLOP/s, whole job
     achieved = flop / (kern_ms * 1e-3) / 1e12            # TFLOP/s, per launch
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, rank, world, Cm)
+    del Cm
     traffic, traffic_src = traffic_from_profiles(n)
-    host_api = bench_host_api(n) if rank == 0 and world == 1 and not args.no_cpu else None
+    host_api = bench_host_api(n) if with_cpu else None
     config1 = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if with_cpu:
         try:
             config1 = bench_config1()
         except Exception as e:  # reported, never required
             config1 = {"error": str(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if with_cpu:
         try:
             cpu = cpu_baseline(n, args.cpu_seconds)
         except Exception as e:  # the baseline is reported, never required

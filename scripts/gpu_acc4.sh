@@ -9,5 +9,5 @@ for r in 1 2; do
   timeout -k 10 120 python -u scripts/train_bwd_once.py --passes 8 > "$out/acc4_$r.txt" || exit 1
   TNS_ACC4=0 timeout -k 10 120 python -u scripts/train_bwd_once.py --passes 8 > "$out/scalar_$r.txt" || exit 1
 done
-timeout -k 10 600 python -u bench.py > "$out/bench_acc4.json" 2> "$out/bench_acc4.err" || exit 1
-TNS_ACC4=0 timeout -k 10 600 python -u bench.py > "$out/bench_scalar.json" 2> "$out/bench_scalar.err" || exit 1
+timeout -k 10 600 python -u bench.py --full > "$out/bench_acc4.json" 2> "$out/bench_acc4.err" || exit 1
+TNS_ACC4=0 timeout -k 10 600 python -u bench.py --full > "$out/bench_scalar.json" 2> "$out/bench_scalar.err" || exit 1

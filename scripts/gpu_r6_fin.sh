@@ -9,4 +9,4 @@ for r in 1 2; do
   timeout -k 10 120 python -u scripts/train_bwd_once.py --passes 8 > "$out/fused$r.txt" || exit 1
   TNS_BN_FUSED=0 timeout -k 10 120 python -u scripts/train_bwd_once.py --passes 8 > "$out/three$r.txt" || exit 1
 done
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 20 --no-cpu > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 20 --no-cpu > "$out/bench.json" 2> "$out/bench.err"

@@ -9,5 +9,5 @@ for r in 1 2; do
   timeout -k 10 120 python -u scripts/train_bwd_once.py --passes 8 > "$out/rule_$r.txt" || exit 1
   TNS_RES_CHL=2048 timeout -k 10 120 python -u scripts/train_bwd_once.py --passes 8 > "$out/c2048_$r.txt" || exit 1
 done
-timeout -k 10 600 python -u bench.py > "$out/bench_rule.json" 2> "$out/bench_rule.err" || exit 1
-TNS_RES_CHL=2048 timeout -k 10 600 python -u bench.py > "$out/bench_2048.json" 2> "$out/bench_2048.err" || exit 1
+timeout -k 10 600 python -u bench.py --full > "$out/bench_rule.json" 2> "$out/bench_rule.err" || exit 1
+TNS_RES_CHL=2048 timeout -k 10 600 python -u bench.py --full > "$out/bench_2048.json" 2> "$out/bench_2048.err" || exit 1
