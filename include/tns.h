@@ -302,6 +302,67 @@ int tns_hip_upsample(tns_ctx* ctx, int64_t aBatch, int64_t aChannels, int64_t ou
 int tns_hip_yolo_forward(tns_ctx* ctx, int64_t batch, int64_t anchors, int64_t classes,
                          int64_t hw, const float* in, float* out);
 
+/* ---- max / local-average pooling (TMaxPoolLayer, nMaxPoolLayer.pas) ----- */
+/* Geometry, shared by the four entries: input [aBatch][c][h][w], output
+ * [aBatch][outC][outH][outW] with outC == c, outH == (h + padding -
+ * kernelSize) div stride_y + 1 and outW likewise with stride_x
+ * (nMaxPoolLayer.pas:107-109).  Window (i, j) covers rows off + i*stride_y ..
+ * + kernelSize - 1 and columns off + j*stride_x .. + kernelSize - 1, off =
+ * -(padding div 2); taps outside the input do not take part.  TNS_ERR_ARG,
+ * before anything is launched or written: a negative size, kernelSize or a
+ * stride below 1, negative padding, outC != c, an output shape other than the
+ * one above, kernelSize beyond the padded input, a plane beyond 2^31 elements,
+ * a null operand where there is work.  maxpool_depth and antialiasing are not
+ * built (the reference's device path has neither).
+ *
+ * tns_hip_maxpool_forward = TNNCuda.forwardMaxPool (nncuda.pas:132), the CPU
+ * loop nMaxPoolLayer.pas:415-451: the window is scanned rows outer, columns
+ * inner, from max = -FLT_MAX, max_i = -1, with a strict `val > max`: the first
+ * maximum in scan order wins, NaN and -inf are never taken, and a window with
+ * nothing above -FLT_MAX gives output -FLT_MAX and index -1.  indexes[out] is
+ * the maximum's element index in the whole input buffer (cur_w + w*(cur_h +
+ * h*(k + b*c))), int64 (TSizeIntTensor); indexes may be null (inference):
+ * only output is written then.
+ *
+ * tns_hip_maxpool_backward = TNNCuda.backwardMaxPool (nncuda.pas:133) plus the
+ * layer's geometry, which the ordered form needs: output (state.delta, the
+ * layer below's delta, [aBatch][outC][h][w]) gets, per element, the delta of
+ * every output whose stored index names it, added one rounding at a time in
+ * ascending output index — the CPU loop's order (nMaxPoolLayer.pas:501-513).
+ * The reference's device kernel scatters `output[index] += delta[id]`
+ * without atomics, a race wherever stride < kernelSize; here one thread owns
+ * an input element and gathers, so the result is deterministic and the CPU's.
+ * Departure: an index of -1 names no element and is ignored (the reference
+ * reads and writes state.delta[-1], out of bounds).  Elements that no index
+ * names keep their bits (nothing is added to them; a 16-byte group without a
+ * named element is not written at all).
+ *
+ * tns_hip_avgpool_forward / _backward: TMaxPoolLayer.forwardAvgPool /
+ * backwardAvgPool (nMaxPoolLayer.pas:465-499, 515-542), which the reference
+ * runs on the CPU only (its GPU branch does nothing for avg pooling).
+ * Forward: the in-range taps summed in scan order, then one division by
+ * their count.  Backward: state.delta[p] += delta[out] / float(kernelSize *
+ * kernelSize) for every window covering p, in ascending output index — the
+ * reference divides by kernelSize^2 here, not by the in-range count.  Also
+ * TNS_ERR_ARG: a geometry in which some window has no tap inside the input
+ * (a zero counter in the reference). */
+int tns_hip_maxpool_forward(tns_ctx* ctx, int64_t aBatch, int64_t outC, int64_t outH,
+                            int64_t outW, const float* input, int64_t c, int64_t h, int64_t w,
+                            int64_t stride_x, int64_t stride_y, int64_t padding,
+                            int64_t kernelSize, int64_t* indexes, float* output);
+int tns_hip_maxpool_backward(tns_ctx* ctx, int64_t aBatch, int64_t outC, int64_t outH,
+                             int64_t outW, float* output, const int64_t* indexes,
+                             const float* delta, int64_t h, int64_t w, int64_t stride_x,
+                             int64_t stride_y, int64_t padding, int64_t kernelSize);
+int tns_hip_avgpool_forward(tns_ctx* ctx, int64_t aBatch, int64_t outC, int64_t outH,
+                            int64_t outW, const float* input, int64_t c, int64_t h, int64_t w,
+                            int64_t stride_x, int64_t stride_y, int64_t padding,
+                            int64_t kernelSize, float* output);
+int tns_hip_avgpool_backward(tns_ctx* ctx, int64_t aBatch, int64_t outC, int64_t outH,
+                             int64_t outW, float* output, const float* delta, int64_t h,
+                             int64_t w, int64_t stride_x, int64_t stride_y, int64_t padding,
+                             int64_t kernelSize);
+
 /* ---- batch norm / softmax (TNNCuda twins, nncuda.pas:1056-1510; CPU
  * semantics ntensors.pas:7687-7830, 8693-8951, 9102-9177,
  * nsoftmaxlayer.pas:83-137).  Data is [groups][channels][blockSize]. ---- */
@@ -621,7 +682,7 @@ int tns_hip_gemm_variant(tns_ctx* ctx, int32_t variant, uint8_t transA, uint8_t 
  * default (pipelineBackward = true): there every access goes through the API.
  * Since round 6 no entry point joins unconditionally during a pipelined
  * pass: the non-conv ones (gemm, im2col / col2im, bias, activation, BLAS-1,
- * addvv & co, shortcut, upsample, yolo, batch norm, softmax, sgd_update)
+ * addvv & co, shortcut, upsample, yolo, pooling, batch norm, softmax, sgd_update)
  * join only when they write a pending dW's delta or input, read or write its
  * weight_updates (or the caller's workspace that dW's im2col fills), or take
  * a context scratch slot the side stream still uses — so TNet.backward's

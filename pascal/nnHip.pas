@@ -12,7 +12,7 @@ unit nnHip;
   Entry points return a status (0 = TNS_OK); every call is checked and a
   failure raises ETnsError with tns_last_error(), as SAFE_CALL raises for
   CUDA (nncuda.pas:216-275).  Methods of TNNCuda<T> that are not on the
-  SGEMM + im2col-convolution hot path (SURVEY.md §8: max-pool, dropout,
+  SGEMM + im2col-convolution hot path (SURVEY.md §8: dropout,
   SWISH, L2 / logistic cost, power, the NVRTC / CUBIN loaders) raise
   ENotSupportedException instead of silently doing nothing.
 
@@ -189,6 +189,20 @@ function tns_hip_upsample(ctx: PTnsCtx; aBatch, aChannels, outHeight, outWidth: 
 function tns_hip_yolo_forward(ctx: PTnsCtx; batch, anchors, classes, hw: int64; input,
   output: THipMem): longint; cdecl; external libtns;
 
+{ max / local-average pooling; indexes = TSizeIntTensor's device data }
+function tns_hip_maxpool_forward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; input: THipMem;
+  c, h, w, stride_x, stride_y, padding, kernelSize: int64; indexes: PInt64;
+  output: THipMem): longint; cdecl; external libtns;
+function tns_hip_maxpool_backward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; output: THipMem;
+  indexes: PInt64; delta: THipMem; h, w, stride_x, stride_y, padding,
+  kernelSize: int64): longint; cdecl; external libtns;
+function tns_hip_avgpool_forward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; input: THipMem;
+  c, h, w, stride_x, stride_y, padding, kernelSize: int64; output: THipMem): longint;
+  cdecl; external libtns;
+function tns_hip_avgpool_backward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; output,
+  delta: THipMem; h, w, stride_x, stride_y, padding, kernelSize: int64): longint;
+  cdecl; external libtns;
+
 { batch norm / softmax }
 function tns_hip_means_and_vars(ctx: PTnsCtx; srcSize, dstSize, groups: int64; src: THipMem;
   offset: int64; means, vars: THipMem): longint; cdecl; external libtns;
@@ -328,7 +342,9 @@ type
     procedure softmaxBatch(const N: SizeInt; const input: TCUMem; const iOffset: SizeInt; const batch, batch_size, groups, group_size, stride: SizeInt; const temp: T; const output: TCUMem; const oOffset: SizeInt);
     procedure crossEntropySoftmax(const N: SizeInt; const pred, truth: TCUMem; delta, error: TCUMem);
     procedure forwardMaxPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; indexes, output: TCUMem);
-    procedure backwardMaxPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const indexes, delta: TCUMem);
+    procedure backwardMaxPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const indexes, delta: TCUMem; const h: SizeInt = 0; const w: SizeInt = 0; const stride_x: SizeInt = 0; const stride_y: SizeInt = 0; const padding: SizeInt = 0; const kernelSize: SizeInt = 0);
+    procedure forwardAvgPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; output: TCUMem);
+    procedure backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const delta: TCUMem; const h, w, stride_x, stride_y, padding, kernelSize: SizeInt);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
     procedure upSample(const aBatch, aChannels, outHeight, outWidth: SizeInt; const &in: TCUMem; const stride: SizeInt; const isForward: longint; const scale: T; const &out: TCUMem; const zeroIn: integer = 0);
@@ -574,12 +590,33 @@ end;
 
 procedure TNNHip<T>.forwardMaxPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; indexes, output: TCUMem);
 begin
-  raise ENotSupportedException.Create('TNNHip.forwardMaxPool: not on the hot path (SURVEY.md §8)')
+  { indexes: the layer's TSizeIntTensor device data (int64 per output), nil
+    in inference }
+  check(tns_hip_maxpool_forward(FCtx, aBatch, outC, outH, outW, THipMem(input), c, h, w, stride_x,
+    stride_y, padding, kernelSize, PInt64(indexes), THipMem(output)))
 end;
 
-procedure TNNHip<T>.backwardMaxPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const indexes, delta: TCUMem);
+procedure TNNHip<T>.backwardMaxPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const indexes, delta: TCUMem; const h: SizeInt; const w: SizeInt; const stride_x: SizeInt; const stride_y: SizeInt; const padding: SizeInt; const kernelSize: SizeInt);
 begin
-  raise ENotSupportedException.Create('TNNHip.backwardMaxPool: not on the hot path (SURVEY.md §8)')
+  { state.delta gets the deltas in the CPU loop's add order (ascending output
+    index) by a gather over the windows covering each input element; that
+    needs the layer's geometry, which TNNCuda's seven parameters do not carry }
+  if kernelSize = 0 then
+    raise ENotSupportedException.Create('TNNHip.backwardMaxPool: the ordered gather needs the layer geometry (pass h, w, stride_x, stride_y, padding, kernelSize; INTEGRATION.md)');
+  check(tns_hip_maxpool_backward(FCtx, aBatch, outC, outH, outW, THipMem(output), PInt64(indexes),
+    THipMem(delta), h, w, stride_x, stride_y, padding, kernelSize))
+end;
+
+procedure TNNHip<T>.forwardAvgPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; output: TCUMem);
+begin
+  check(tns_hip_avgpool_forward(FCtx, aBatch, outC, outH, outW, THipMem(input), c, h, w, stride_x,
+    stride_y, padding, kernelSize, THipMem(output)))
+end;
+
+procedure TNNHip<T>.backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const delta: TCUMem; const h, w, stride_x, stride_y, padding, kernelSize: SizeInt);
+begin
+  check(tns_hip_avgpool_backward(FCtx, aBatch, outC, outH, outW, THipMem(output), THipMem(delta),
+    h, w, stride_x, stride_y, padding, kernelSize))
 end;
 
 procedure TNNHip<T>.im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);

@@ -200,6 +200,15 @@ PROTOTYPES.update({
                                                       fptr, i64, i64, i64]),
     "tns_set_op_devices": (C.c_int, [C.POINTER(i32), i32]),
     "tns_hip_yolo_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr]),
+    # pooling: the indexes operand is an int64 device buffer
+    "tns_hip_maxpool_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, i64, i64, i64, i64, i64,
+                                          i64, i64, vp, fptr]),
+    "tns_hip_maxpool_backward": (C.c_int, [vp, i64, i64, i64, i64, fptr, vp, fptr, i64, i64, i64,
+                                           i64, i64, i64]),
+    "tns_hip_avgpool_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, i64, i64, i64, i64, i64,
+                                          i64, i64, fptr]),
+    "tns_hip_avgpool_backward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64,
+                                           i64, i64, i64]),
     "tns_hip_means_and_vars": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),
     "tns_hip_means": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr]),
     "tns_hip_variances": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),

@@ -1268,6 +1268,118 @@ int tns_hip_yolo_forward(tns_ctx* c, int64_t batch, int64_t anchors, int64_t cla
   return hip_status(launch_yolo(batch, (int)anchors, (int)classes, hw, in, out, c->stream), "yolo");
 }
 
+// TNNCuda.forwardMaxPool / backwardMaxPool (nncuda.pas:132-133) and the local
+// average pool over the same geometry
+namespace {
+// TMaxPoolLayer.Create's shapes (nMaxPoolLayer.pas:107-109) restated and held
+// against the caller's; avg: no window without an in-range tap (the reference
+// divides by a zero counter there).  *planes = aBatch*outC, *nin / *nout the
+// whole buffers' element counts.
+int pool_geom(const char* what, bool avg, int64_t aBatch, int64_t outC, int64_t outH, int64_t outW,
+              int64_t c, int64_t h, int64_t w, int64_t sx, int64_t sy, int64_t padding,
+              int64_t size, PoolGeom* g, int64_t* planes, int64_t* nin, int64_t* nout) {
+  const int64_t lim = 0x3fffffff;
+  if (aBatch < 0 || outC < 0 || outH < 0 || outW < 0 || c < 0 || h < 0 || w < 0 || size < 1 ||
+      sx < 1 || sy < 1 || padding < 0)
+    return set_error(TNS_ERR_ARG, "%s: negative size, or kernelSize / stride below 1", what);
+  if (aBatch > lim || outC > lim || h > lim || w > lim || size > lim || sx > lim || sy > lim ||
+      padding > lim)
+    return set_error(TNS_ERR_ARG, "%s: dimension beyond 2^30", what);
+  if (outC != c) return set_error(TNS_ERR_ARG, "%s: outC %lld != c %lld", what, (long long)outC,
+                                  (long long)c);
+  if (h + padding < size || w + padding < size)
+    return set_error(TNS_ERR_ARG, "%s: kernelSize %lld exceeds the padded input", what,
+                     (long long)size);
+  const int64_t oh = (h + padding - size) / sy + 1, ow = (w + padding - size) / sx + 1;
+  if (outH != oh || outW != ow)
+    return set_error(TNS_ERR_ARG, "%s: output %lldx%lld, the geometry gives %lldx%lld", what,
+                     (long long)outH, (long long)outW, (long long)oh, (long long)ow);
+  if (h * w > 0x7fffffff || oh * ow > 0x7fffffff)
+    return set_error(TNS_ERR_ARG, "%s: plane beyond 2^31 elements", what);
+  const int64_t plane = std::max<int64_t>(std::max(h * w, oh * ow), 1);
+  if (aBatch * outC > INT64_MAX / 8 / plane)
+    return set_error(TNS_ERR_ARG, "%s: buffer beyond 2^63 bytes", what);
+  const int64_t off = -(padding / 2);
+  if (avg && (off + size - 1 < 0 || off + (oh - 1) * sy > h - 1 || off + (ow - 1) * sx > w - 1))
+    return set_error(TNS_ERR_ARG, "%s: a window has no tap inside the input", what);
+  *g = PoolGeom{(int)h, (int)w, (int)oh, (int)ow, (int)size, (int)sx, (int)sy, (int)off};
+  *planes = aBatch * outC;
+  *nin = *planes * h * w;
+  *nout = *planes * oh * ow;
+  return TNS_OK;
+}
+}  // namespace
+
+int tns_hip_maxpool_forward(tns_ctx* c, int64_t aBatch, int64_t outC, int64_t outH, int64_t outW,
+                            const float* input, int64_t ch, int64_t h, int64_t w,
+                            int64_t stride_x, int64_t stride_y, int64_t padding,
+                            int64_t kernelSize, int64_t* indexes, float* output) {
+  PoolGeom g;
+  int64_t planes, nin, nout;
+  if (int r = pool_geom("maxpool forward", false, aBatch, outC, outH, outW, ch, h, w, stride_x,
+                        stride_y, padding, kernelSize, &g, &planes, &nin, &nout))
+    return r;
+  if (nout > 0 && (!output || (nin > 0 && !input)))
+    return set_error(TNS_ERR_ARG, "maxpool forward: null operand");
+  // (the int64 indexes' byte extent: two floats per index)
+  if (int r = check_ops(c, {span(output, nout), span(reinterpret_cast<float*>(indexes), 2 * nout)},
+                        {span(input, nin)}))
+    return r;
+  return hip_status(launch_maxpool_forward(planes, g, input, output, indexes, c->stream),
+                    "maxpool forward");
+}
+
+int tns_hip_maxpool_backward(tns_ctx* c, int64_t aBatch, int64_t outC, int64_t outH, int64_t outW,
+                             float* output, const int64_t* indexes, const float* delta, int64_t h,
+                             int64_t w, int64_t stride_x, int64_t stride_y, int64_t padding,
+                             int64_t kernelSize) {
+  PoolGeom g;
+  int64_t planes, nin, nout;
+  if (int r = pool_geom("maxpool backward", false, aBatch, outC, outH, outW, outC, h, w, stride_x,
+                        stride_y, padding, kernelSize, &g, &planes, &nin, &nout))
+    return r;
+  if (nout > 0 && nin > 0 && (!output || !indexes || !delta))
+    return set_error(TNS_ERR_ARG, "maxpool backward: null operand");
+  if (int r = check_ops(c, {span(output, nin)},
+                        {span(reinterpret_cast<const float*>(indexes), 2 * nout),
+                         span(delta, nout)}))
+    return r;
+  return hip_status(launch_maxpool_backward(planes, g, output, indexes, delta, c->stream),
+                    "maxpool backward");
+}
+
+int tns_hip_avgpool_forward(tns_ctx* c, int64_t aBatch, int64_t outC, int64_t outH, int64_t outW,
+                            const float* input, int64_t ch, int64_t h, int64_t w,
+                            int64_t stride_x, int64_t stride_y, int64_t padding,
+                            int64_t kernelSize, float* output) {
+  PoolGeom g;
+  int64_t planes, nin, nout;
+  if (int r = pool_geom("avgpool forward", true, aBatch, outC, outH, outW, ch, h, w, stride_x,
+                        stride_y, padding, kernelSize, &g, &planes, &nin, &nout))
+    return r;
+  if (nout > 0 && (!output || !input))
+    return set_error(TNS_ERR_ARG, "avgpool forward: null operand");
+  if (int r = check_ops(c, {span(output, nout)}, {span(input, nin)})) return r;
+  return hip_status(launch_avgpool_forward(planes, g, input, output, c->stream),
+                    "avgpool forward");
+}
+
+int tns_hip_avgpool_backward(tns_ctx* c, int64_t aBatch, int64_t outC, int64_t outH, int64_t outW,
+                             float* output, const float* delta, int64_t h, int64_t w,
+                             int64_t stride_x, int64_t stride_y, int64_t padding,
+                             int64_t kernelSize) {
+  PoolGeom g;
+  int64_t planes, nin, nout;
+  if (int r = pool_geom("avgpool backward", true, aBatch, outC, outH, outW, outC, h, w, stride_x,
+                        stride_y, padding, kernelSize, &g, &planes, &nin, &nout))
+    return r;
+  if (nout > 0 && (!output || !delta))
+    return set_error(TNS_ERR_ARG, "avgpool backward: null operand");
+  if (int r = check_ops(c, {span(output, nin)}, {span(delta, nout)})) return r;
+  return hip_status(launch_avgpool_backward(planes, g, output, delta, c->stream),
+                    "avgpool backward");
+}
+
 int tns_hip_clamp(tns_ctx* c, int64_t N, float alpha, const float* src, float* dst,
                   int64_t stride, int64_t offset) {
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, N, stride)},

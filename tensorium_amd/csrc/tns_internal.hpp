@@ -320,6 +320,21 @@ hipError_t launch_upsample(int64_t planes, int H, int W, int stride, float scale
                            float* out, hipStream_t s);
 hipError_t launch_upsample_backward(int64_t planes, int H, int W, int stride, float scale,
                                    float* in, const float* out, int zero, hipStream_t s);
+// pool.hip: max / local-average pooling.  One plane is h x w in, outH x outW
+// out; windows of size x size taps start at (off + i*sy, off + j*sx), off =
+// -(padding div 2).  The callers have checked that plane sizes, h + padding
+// and w + padding fit an int.
+struct PoolGeom {
+  int h, w, outH, outW, size, sx, sy, off;
+};
+hipError_t launch_maxpool_forward(int64_t planes, const PoolGeom& g, const float* in, float* out,
+                                  int64_t* indexes, hipStream_t s);
+hipError_t launch_avgpool_forward(int64_t planes, const PoolGeom& g, const float* in, float* out,
+                                  hipStream_t s);
+hipError_t launch_maxpool_backward(int64_t planes, const PoolGeom& g, float* state_delta,
+                                   const int64_t* indexes, const float* delta, hipStream_t s);
+hipError_t launch_avgpool_backward(int64_t planes, const PoolGeom& g, float* state_delta,
+                                   const float* delta, hipStream_t s);
 // TNNCuda addvv/subvv/mulvv/fmavv (op 0..3), fmavss, inverseSqrt
 hipError_t launch_vv(int op, int64_t n, const float* a, int64_t inca, const float* b, int64_t incb,
                      const float* c, int64_t incc, float* d, int64_t incd, hipStream_t s);

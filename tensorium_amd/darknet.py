@@ -10,7 +10,9 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   (``pad=1`` => padding = size div 2, nparser.pas:186-189; out = (in + 2p - k)
   div stride + 1, nConvolutionLayer.pas:92-100), shortcut (TAddLayer,
   naddlayer.pas), route (TConcatLayer, nconcatlayer.pas), upsample
-  (TUpSampleLayer, nupsamplelayer.pas) and yolo (TYoloLayer, nyololayer.pas).
+  (TUpSampleLayer, nupsamplelayer.pas), yolo (TYoloLayer, nyololayer.pas) and
+  maxpool / local_avgpool (TMaxPoolLayer, nMaxPoolLayer.pas:107-109; options
+  as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292).
 * ``load_weights`` / ``write_weights``: the darknet .weights layout read by
   TDarknetParser.loadWeights (nparser.pas:1275-1330): int32 major, minor,
   revision, then ``seen`` as uint64 when major*10+minor >= 2 (else uint32),
@@ -70,7 +72,8 @@ def parse_cfg(text: str) -> list[Section]:
 @dataclass
 class Layer:
     index: int
-    kind: str            # convolutional | shortcut | route | upsample | yolo
+    kind: str            # convolutional | shortcut | route | upsample | yolo |
+                         # maxpool | local_avgpool
     c: int               # input channels / height / width
     h: int
     w: int
@@ -86,6 +89,12 @@ class Layer:
     inputs: tuple = ()   # shortcut: (from,), route: the layers, others: ()
     anchors: int = 0     # yolo: anchors of this scale (len(mask))
     classes: int = 0
+    stride_x: int = 0    # pools: the two strides (pad holds their padding);
+    stride_y: int = 0    # every other layer: both = stride
+
+    def __post_init__(self):
+        self.stride_x = self.stride_x or self.stride
+        self.stride_y = self.stride_y or self.stride
 
     @property
     def out_size(self) -> int:
@@ -137,6 +146,27 @@ class Network:
                 lay = Layer(i, "yolo", c, h, w, c, h, w, anchors=len(mask), classes=classes)
                 if c != len(mask) * (classes + 5):
                     raise ValueError(f"yolo layer {i}: {c} channels for {len(mask)} anchors")
+            elif sec.kind in ("maxpool", "max", "local_avgpool"):
+                # parseMaxPool / parseLocalAvgPool (nparser.pas:248-292), shapes
+                # TMaxPoolLayer.Create (nMaxPoolLayer.pas:79-82, 107-109)
+                kind = "local_avgpool" if sec.kind == "local_avgpool" else "maxpool"
+                stride = sec.int("stride", 1)
+                sx, sy = sec.int("stride_x", stride), sec.int("stride_y", stride)
+                size = sec.int("size", stride)
+                padding = sec.int("padding", size - 1)
+                if kind == "maxpool" and (sec.int("maxpool_depth", 0)
+                                          or sec.int("antialiasing", 0)):
+                    raise ValueError(f"[{sec.kind}] layer {i}: maxpool_depth / antialiasing are "
+                                     "not built (the reference's device path has neither)")
+                if h * w * c == 0:
+                    raise ValueError(f"Layer before [{sec.kind}] layer must output image.")
+                sx, sy = sx or size, sy or size
+                if size < 1 or padding < 0 or h + padding < size or w + padding < size:
+                    raise ValueError(f"[{sec.kind}] layer {i}: size {size}, padding {padding} on "
+                                     f"{h}x{w}")
+                lay = Layer(i, kind, c, h, w, c, (h + padding - size) // sy + 1,
+                            (w + padding - size) // sx + 1, size=size, stride=sx, pad=padding,
+                            stride_x=sx, stride_y=sy)
             else:
                 raise ValueError(f"[Parser][{sec.kind}] layer is not yet implemented!")
             self.layers.append(lay)
@@ -193,6 +223,41 @@ def yolov3_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
     for _ in range(3):
         conv(128, 1); conv(256, 3)
     conv(det, 1, act="linear", bn=False)
+    yolo("0,1,2")
+    return "\n".join(out)
+
+
+def yolov3_tiny_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
+    """The darknet YOLOv3-tiny network (the public yolov3-tiny.cfg structure):
+    six conv + maxpool stages, the last pool 2x2 with stride 1, and two
+    detection scales."""
+    out = [f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={size}\nheight={size}\nchannels=3\n"]
+
+    def conv(f, k, act="leaky", bn=True):
+        out.append(f"[convolutional]\n{'batch_normalize=1' + chr(10) if bn else ''}"
+                   f"filters={f}\nsize={k}\nstride=1\npad=1\nactivation={act}\n")
+
+    def maxpool(stride):
+        out.append(f"[maxpool]\nsize=2\nstride={stride}\n")
+
+    anchors = "10,14, 23,27, 37,58, 81,82, 135,169, 344,319"
+
+    def yolo(mask):
+        out.append(f"[yolo]\nmask = {mask}\nanchors = {anchors}\nclasses={classes}\nnum=6\n"
+                   "jitter=.3\nignore_thresh = .7\ntruth_thresh = 1\nrandom=1\n")
+
+    det = 3 * (classes + 5)
+    for f in (16, 32, 64, 128, 256):
+        conv(f, 3); maxpool(2)
+    conv(512, 3); maxpool(1)
+    conv(1024, 3)
+    conv(256, 1); conv(512, 3); conv(det, 1, act="linear", bn=False)
+    yolo("3,4,5")
+    out.append("[route]\nlayers = -4\n")
+    conv(128, 1)
+    out.append("[upsample]\nstride=2\n")
+    out.append("[route]\nlayers = -1, 8\n")
+    conv(256, 3); conv(det, 1, act="linear", bn=False)
     yolo("0,1,2")
     return "\n".join(out)
 
@@ -321,6 +386,12 @@ class HipDarknet:
                 hip.upSample(B, l.c, l.h, l.w, prev, l.stride, 1, 1.0, out)
             elif l.kind == "yolo":
                 hip.yoloForward(B, l.anchors, l.classes, l.h * l.w, prev, out)
+            elif l.kind == "maxpool":  # inference: no indexes
+                hip.forwardMaxPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
+                                   l.stride_y, l.pad, l.size, None, out)
+            elif l.kind == "local_avgpool":
+                hip.forwardAvgPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
+                                   l.stride_y, l.pad, l.size, out)
             prev = out
         return self.out
 
@@ -347,7 +418,11 @@ class HipDarknetTrain:
     * yolo (TYoloLayer.backwardGPU, nyololayer.pas:1112-1125): ``axpy`` of its
       delta (scaled by lossScale*deltaNormalizer) into state.delta.  The yolo
       loss that fills that delta during the training forward is out of scope
-      (DESIGN.md); ``set_yolo_deltas`` supplies it.
+      (DESIGN.md); ``set_yolo_deltas`` supplies it;
+    * maxpool / local_avgpool (TMaxPoolLayer.backwardGPU, nMaxPoolLayer.pas:
+      689-706; CPU loops 501-542): ``backwardMaxPool`` with the indexes its
+      forward stored, or ``backwardAvgPool``, accumulating into state.delta;
+      nothing when the pool is layer 0 (no state.delta).
 
     Convolutions with batch norm run ``convForwardTrain`` (training-time BN,
     nbaselayer.pas:336-370) in the forward, the heads ``convForward``.  No
@@ -362,6 +437,9 @@ class HipDarknetTrain:
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
         self.out = [torch.zeros(B * l.out_size, device=dev) for l in net.layers]
         self.delta = [torch.zeros(B * l.out_size, device=dev) for l in net.layers]
+        # a maxpool's indexes (TSizeIntTensor, int64): filled by its forward
+        self.indexes = {l.index: torch.zeros(B * l.out_size, dtype=torch.int64, device=dev)
+                        for l in net.layers if l.kind == "maxpool"}
         self.conv = {}
         ws = 1
         for l, p in zip(net.convs(), params):
@@ -412,6 +490,12 @@ class HipDarknetTrain:
                 hip.upSample(B, l.c, l.h, l.w, prev, l.stride, 1, 1.0, out)
             elif l.kind == "yolo":
                 hip.yoloForward(B, l.anchors, l.classes, l.h * l.w, prev, out)
+            elif l.kind == "maxpool":
+                hip.forwardMaxPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
+                                   l.stride_y, l.pad, l.size, self.indexes[l.index], out)
+            elif l.kind == "local_avgpool":
+                hip.forwardAvgPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
+                                   l.stride_y, l.pad, l.size, out)
             prev = out
         return self.out
 
@@ -458,5 +542,11 @@ class HipDarknetTrain:
                 hip.upSample(B, l.c, l.h, l.w, sd, l.stride, 0, 1.0, d)
             elif l.kind == "yolo":
                 hip.axpy(sd.numel(), self.loss_scale, d, 0, 1, sd, 0, 1)
+            elif l.kind == "maxpool" and sd is not None:
+                hip.backwardMaxPool(B, l.out_c, l.out_h, l.out_w, sd, self.indexes[i], d, l.h, l.w,
+                                    l.stride_x, l.stride_y, l.pad, l.size)
+            elif l.kind == "local_avgpool" and sd is not None:
+                hip.backwardAvgPool(B, l.out_c, l.out_h, l.out_w, sd, d, l.h, l.w, l.stride_x,
+                                    l.stride_y, l.pad, l.size)
             if on_backward is not None:
                 on_backward(l)

@@ -41,6 +41,21 @@ def _ptr(x):
     raise TnsError(f"unsupported buffer type {type(x)!r}")
 
 
+def _iptr(x):
+    """The one int64 operand (a maxpool's indexes, TSizeIntTensor)."""
+    if x is None or isinstance(x, int):
+        return x
+    if torch is not None and isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            raise TnsError("TNNHip expects device (cuda) tensors")
+        if x.dtype != torch.int64:
+            raise TnsError(f"TNNHip expects an int64 indexes tensor, got {x.dtype}")
+        if not x.is_contiguous():
+            raise TnsError("TNNHip expects contiguous tensors")
+        return x.data_ptr()
+    raise TnsError(f"unsupported buffer type {type(x)!r}")
+
+
 class TNNHip:
     """HIP twin of TNNCuda<single> (one context = one device + one stream)."""
 
@@ -228,6 +243,37 @@ class TNNHip:
         check(self.lib.tns_hip_upsample(self.ctx, aBatch, aChannels, outHeight, outWidth,
                                         _ptr(in_), stride, int(isForward), float(scale),
                                         _ptr(out), int(zeroIn)))
+
+    def forwardMaxPool(self, aBatch, outC, outH, outW, input, c, h, w, stride_x, stride_y, padding,
+                       kernelSize, indexes, output):
+        """TNNCuda.forwardMaxPool (nncuda.pas:132); indexes: int64 device
+        tensor, or None (inference: only output is written)."""
+        check(self.lib.tns_hip_maxpool_forward(self.ctx, aBatch, outC, outH, outW, _ptr(input), c,
+                                               h, w, stride_x, stride_y, padding, kernelSize,
+                                               _iptr(indexes), _ptr(output)))
+
+    def backwardMaxPool(self, aBatch, outC, outH, outW, output, indexes, delta, h, w, stride_x,
+                        stride_y, padding, kernelSize):
+        """TNNCuda.backwardMaxPool (nncuda.pas:133) plus the layer's geometry
+        (the gather in the CPU's add order needs it); output = state.delta."""
+        check(self.lib.tns_hip_maxpool_backward(self.ctx, aBatch, outC, outH, outW, _ptr(output),
+                                                _iptr(indexes), _ptr(delta), h, w, stride_x,
+                                                stride_y, padding, kernelSize))
+
+    def forwardAvgPool(self, aBatch, outC, outH, outW, input, c, h, w, stride_x, stride_y, padding,
+                       kernelSize, output):
+        """TMaxPoolLayer.forwardAvgPool (nMaxPoolLayer.pas:465-499)."""
+        check(self.lib.tns_hip_avgpool_forward(self.ctx, aBatch, outC, outH, outW, _ptr(input), c,
+                                               h, w, stride_x, stride_y, padding, kernelSize,
+                                               _ptr(output)))
+
+    def backwardAvgPool(self, aBatch, outC, outH, outW, output, delta, h, w, stride_x, stride_y,
+                        padding, kernelSize):
+        """TMaxPoolLayer.backwardAvgPool (nMaxPoolLayer.pas:515-542);
+        output = state.delta."""
+        check(self.lib.tns_hip_avgpool_backward(self.ctx, aBatch, outC, outH, outW, _ptr(output),
+                                                _ptr(delta), h, w, stride_x, stride_y, padding,
+                                                kernelSize))
 
     def addvv(self, N, src1, src1Offset, inca, src2, src2Offset, incb, dst, dstOffset, incc):
         check(self.lib.tns_hip_addvv(self.ctx, N, _ptr(src1), src1Offset, inca, _ptr(src2),
