@@ -363,6 +363,38 @@ int tns_hip_avgpool_backward(tns_ctx* ctx, int64_t aBatch, int64_t outC, int64_t
                              int64_t w, int64_t stride_x, int64_t stride_y, int64_t padding,
                              int64_t kernelSize);
 
+/* ---- dropout and the elementwise loss heads (heads.hip) ----
+ * tns_hip_dropout_forward = TNNCuda.forwardDropout, the reference's device
+ * kernel (cuda_sgemm.cu:1617-1645), a pure function of (seed, i) — the CPU
+ * layer draws from Pascal's random(), which cannot be reproduced.  Per
+ * element i (a 64-bit index):
+ *   x = uint64(seed) + i           (seed in [0, 2^32); the sum does not wrap)
+ *   x ^= x >> 12; x ^= x << 25; x ^= x >> 27; x *= 0x2545F4914F6CDD1D
+ *   rnd[i] = float(x mod 2^28) / 2^28     (conversion to nearest even)
+ *   dst[i] = rnd[i] < probability ? +0.0f : src[i] * scale
+ * A dropped element is +0.0f whatever src held (NaN, Inf included).
+ * tns_hip_dropout_backward (cuda_sgemm.cu:1647-1653) is the same select over
+ * the stored rnd.  Both work in place: src == dst is how the reference calls
+ * them (ndropoutlayer.pas:162, 170).  TNS_ERR_ARG, before any launch: N < 0,
+ * seed outside [0, 2^32), a null operand with N > 0, rnd overlapping src or
+ * dst, src and dst overlapping other than exactly.  N == 0 does nothing.
+ *
+ * tns_hip_cost_l2 = TNNCuda.costL2 (cuda_sgemm.cu:1655-1662): r = truth -
+ * pred; delta = r; error = r * r, each one rounding.
+ *
+ * tns_hip_cross_entropy_logistic = TNNCuda.crossEntropyLogistic, the CPU
+ * statement (nlogisticlayer.pas:72-77): delta = t - p; error = -t*ln(max(p,
+ * eps)) - (1-t)*ln(max(1-p, eps)), eps = 1e-6f; max, 1-p and 1-t in float,
+ * the logs, products and subtraction in double, rounded once to float. */
+int tns_hip_dropout_forward(tns_ctx* ctx, int64_t N, int64_t seed, float probability,
+                            float scale, const float* src, float* rnd, float* dst);
+int tns_hip_dropout_backward(tns_ctx* ctx, int64_t N, float probability, float scale,
+                             const float* src, const float* rnd, float* dst);
+int tns_hip_cost_l2(tns_ctx* ctx, int64_t N, const float* pred, const float* truth,
+                    float* delta, float* error);
+int tns_hip_cross_entropy_logistic(tns_ctx* ctx, int64_t N, const float* pred,
+                                   const float* truth, float* delta, float* error);
+
 /* ---- batch norm / softmax (TNNCuda twins, nncuda.pas:1056-1510; CPU
  * semantics ntensors.pas:7687-7830, 8693-8951, 9102-9177,
  * nsoftmaxlayer.pas:83-137).  Data is [groups][channels][blockSize]. ---- */

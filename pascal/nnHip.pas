@@ -12,9 +12,9 @@ unit nnHip;
   Entry points return a status (0 = TNS_OK); every call is checked and a
   failure raises ETnsError with tns_last_error(), as SAFE_CALL raises for
   CUDA (nncuda.pas:216-275).  Methods of TNNCuda<T> that are not on the
-  SGEMM + im2col-convolution hot path (SURVEY.md §8: dropout,
-  SWISH, L2 / logistic cost, power, the NVRTC / CUBIN loaders) raise
-  ENotSupportedException instead of silently doing nothing.
+  SGEMM + im2col-convolution hot path (SURVEY.md §8: SWISH, power, the
+  NVRTC / CUBIN loaders) raise ENotSupportedException instead of silently
+  doing nothing.
 
   tests/test_pascal_unit.py cross-checks every external declaration here
   against include/tns.h (name, parameter count, parameter widths, result). }
@@ -202,6 +202,16 @@ function tns_hip_avgpool_forward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; 
 function tns_hip_avgpool_backward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; output,
   delta: THipMem; h, w, stride_x, stride_y, padding, kernelSize: int64): longint;
   cdecl; external libtns;
+
+{ dropout (seed in [0, 2^32)) and the elementwise loss heads }
+function tns_hip_dropout_forward(ctx: PTnsCtx; N, seed: int64; probability, scale: single; src,
+  rnd, dst: THipMem): longint; cdecl; external libtns;
+function tns_hip_dropout_backward(ctx: PTnsCtx; N: int64; probability, scale: single; src, rnd,
+  dst: THipMem): longint; cdecl; external libtns;
+function tns_hip_cost_l2(ctx: PTnsCtx; N: int64; pred, truth, delta, error: THipMem): longint;
+  cdecl; external libtns;
+function tns_hip_cross_entropy_logistic(ctx: PTnsCtx; N: int64; pred, truth, delta,
+  error: THipMem): longint; cdecl; external libtns;
 
 { batch norm / softmax }
 function tns_hip_means_and_vars(ctx: PTnsCtx; srcSize, dstSize, groups: int64; src: THipMem;
@@ -563,7 +573,8 @@ end;
 
 procedure TNNHip<T>.crossEntropyLogistic(const N: SizeInt; const pred, truth: TCUMem; delta, error: TCUMem);
 begin
-  raise ENotSupportedException.Create('TNNHip.crossEntropyLogistic: not on the hot path (SURVEY.md §8)')
+  check(tns_hip_cross_entropy_logistic(FCtx, N, THipMem(pred), THipMem(truth), THipMem(delta),
+    THipMem(error)))
 end;
 
 procedure TNNHip<T>.fill(const N: SizeInt; const x: TCUMem; const offset: SizeInt; const val: T; const stride: SizeInt);
@@ -700,18 +711,22 @@ begin
 end;
 
 procedure TNNHip<T>.forwardDropout(const N: SizeInt; const src: TCUMem; const probability, scale: T; rnd: TCUMem; dst: TCUMem);
+var seed: int64;
 begin
-  raise ENotSupportedException.Create('TNNHip.forwardDropout: not on the hot path (SURVEY.md §8)')
+  seed := random($10000000); // next randSeed, as nncuda.pas:1521
+  check(tns_hip_dropout_forward(FCtx, N, seed, s(probability), s(scale), THipMem(src),
+    THipMem(rnd), THipMem(dst)))
 end;
 
 procedure TNNHip<T>.backwardDropout(const N: SizeInt; const src: TCUMem; const probability, scale: T; const rnd: TCUMem; dst: TCUMem);
 begin
-  raise ENotSupportedException.Create('TNNHip.backwardDropout: not on the hot path (SURVEY.md §8)')
+  check(tns_hip_dropout_backward(FCtx, N, s(probability), s(scale), THipMem(src), THipMem(rnd),
+    THipMem(dst)))
 end;
 
 procedure TNNHip<T>.costL2(const N: SizeInt; const pred, truth, delta, error: TCUMem);
 begin
-  raise ENotSupportedException.Create('TNNHip.costL2: not on the hot path (SURVEY.md §8)')
+  check(tns_hip_cost_l2(FCtx, N, THipMem(pred), THipMem(truth), THipMem(delta), THipMem(error)))
 end;
 
 procedure TNNHip<T>.clamp(const N: SizeInt; const alpha: T; const src, dst: TCUMem; const stride: SizeInt; offset: SizeInt);

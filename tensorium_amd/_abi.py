@@ -209,6 +209,11 @@ PROTOTYPES.update({
                                           i64, i64, fptr]),
     "tns_hip_avgpool_backward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64,
                                            i64, i64, i64]),
+    # dropout (the seed an int64 in [0, 2^32)) and the elementwise loss heads
+    "tns_hip_dropout_forward": (C.c_int, [vp, i64, i64, f32, f32, fptr, fptr, fptr]),
+    "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),
+    "tns_hip_cost_l2": (C.c_int, [vp, i64, fptr, fptr, fptr, fptr]),
+    "tns_hip_cross_entropy_logistic": (C.c_int, [vp, i64, fptr, fptr, fptr, fptr]),
     "tns_hip_means_and_vars": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),
     "tns_hip_means": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr]),
     "tns_hip_variances": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),

@@ -1380,6 +1380,76 @@ int tns_hip_avgpool_backward(tns_ctx* c, int64_t aBatch, int64_t outC, int64_t o
                     "avgpool backward");
 }
 
+// ---- dropout / loss heads (heads.hip) -------------------------------------------
+namespace {
+
+// src == dst exactly is the reference's in-place call; any other meeting of
+// the three operands would make a result depend on the thread order
+int dropout_operands(const char* what, int64_t N, const float* src, const float* rnd,
+                     const float* dst) {
+  if (N < 0) return set_error(TNS_ERR_ARG, "%s: N = %lld", what, (long long)N);
+  if (N == 0) return TNS_OK;
+  if (!src || !rnd || !dst) return set_error(TNS_ERR_ARG, "%s: null operand", what);
+  auto meet = [N](const float* a, const float* b) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)N * sizeof(float);
+    return x < y + len && y < x + len;
+  };
+  if (meet(rnd, src) || meet(rnd, dst))
+    return set_error(TNS_ERR_ARG, "%s: rnd overlaps src or dst", what);
+  if (src != dst && meet(src, dst))
+    return set_error(TNS_ERR_ARG, "%s: src and dst overlap without being the same buffer", what);
+  return TNS_OK;
+}
+
+}  // namespace
+
+int tns_hip_dropout_forward(tns_ctx* c, int64_t N, int64_t seed, float probability, float scale,
+                            const float* src, float* rnd, float* dst) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (int r = dropout_operands("dropout forward", N, src, rnd, dst)) return r;
+  if (seed < 0 || seed > (int64_t)0xFFFFFFFFll)
+    return set_error(TNS_ERR_ARG, "dropout forward: seed %lld outside [0, 2^32)", (long long)seed);
+  if (N == 0) return TNS_OK;
+  if (int r = check_ops(c, {span(dst, N), span(rnd, N)}, {span(src, N)})) return r;
+  return hip_status(launch_dropout_forward(N, (uint32_t)seed, probability, scale, src, rnd, dst,
+                                           c->stream),
+                    "dropout forward");
+}
+
+int tns_hip_dropout_backward(tns_ctx* c, int64_t N, float probability, float scale,
+                             const float* src, const float* rnd, float* dst) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (int r = dropout_operands("dropout backward", N, src, rnd, dst)) return r;
+  if (N == 0) return TNS_OK;
+  if (int r = check_ops(c, {span(dst, N)}, {span(src, N), span(rnd, N)})) return r;
+  return hip_status(launch_dropout_backward(N, probability, scale, src, rnd, dst, c->stream),
+                    "dropout backward");
+}
+
+int tns_hip_cost_l2(tns_ctx* c, int64_t N, const float* pred, const float* truth, float* delta,
+                    float* error) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (N < 0) return set_error(TNS_ERR_ARG, "costL2: N = %lld", (long long)N);
+  if (N == 0) return TNS_OK;
+  if (!pred || !truth || !delta || !error) return set_error(TNS_ERR_ARG, "costL2: null operand");
+  if (int r = check_ops(c, {span(delta, N), span(error, N)}, {span(pred, N), span(truth, N)}))
+    return r;
+  return hip_status(launch_cost_l2(N, pred, truth, delta, error, c->stream), "costL2");
+}
+
+int tns_hip_cross_entropy_logistic(tns_ctx* c, int64_t N, const float* pred, const float* truth,
+                                   float* delta, float* error) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (N < 0) return set_error(TNS_ERR_ARG, "crossEntropyLogistic: N = %lld", (long long)N);
+  if (N == 0) return TNS_OK;
+  if (!pred || !truth || !delta || !error)
+    return set_error(TNS_ERR_ARG, "crossEntropyLogistic: null operand");
+  if (int r = check_ops(c, {span(delta, N), span(error, N)}, {span(pred, N), span(truth, N)}))
+    return r;
+  return hip_status(launch_xent_logistic(N, pred, truth, delta, error, c->stream),
+                    "crossEntropyLogistic");
+}
+
 int tns_hip_clamp(tns_ctx* c, int64_t N, float alpha, const float* src, float* dst,
                   int64_t stride, int64_t offset) {
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, N, stride)},

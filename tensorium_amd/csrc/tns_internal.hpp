@@ -335,6 +335,16 @@ hipError_t launch_maxpool_backward(int64_t planes, const PoolGeom& g, float* sta
                                    const int64_t* indexes, const float* delta, hipStream_t s);
 hipError_t launch_avgpool_backward(int64_t planes, const PoolGeom& g, float* state_delta,
                                    const float* delta, hipStream_t s);
+// heads.hip: dropout (rnd a pure function of seed + i; src == dst allowed)
+// and the elementwise loss heads
+hipError_t launch_dropout_forward(int64_t n, uint32_t seed, float probability, float scale,
+                                  const float* src, float* rnd, float* dst, hipStream_t s);
+hipError_t launch_dropout_backward(int64_t n, float probability, float scale, const float* src,
+                                   const float* rnd, float* dst, hipStream_t s);
+hipError_t launch_cost_l2(int64_t n, const float* pred, const float* truth, float* delta,
+                          float* error, hipStream_t s);
+hipError_t launch_xent_logistic(int64_t n, const float* pred, const float* truth, float* delta,
+                                float* error, hipStream_t s);
 // TNNCuda addvv/subvv/mulvv/fmavv (op 0..3), fmavss, inverseSqrt
 hipError_t launch_vv(int op, int64_t n, const float* a, int64_t inca, const float* b, int64_t incb,
                      const float* c, int64_t incc, float* d, int64_t incd, hipStream_t s);

@@ -12,13 +12,18 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   naddlayer.pas), route (TConcatLayer, nconcatlayer.pas), upsample
   (TUpSampleLayer, nupsamplelayer.pas), yolo (TYoloLayer, nyololayer.pas) and
   maxpool / local_avgpool (TMaxPoolLayer, nMaxPoolLayer.pas:107-109; options
-  as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292).
+  as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292), and the
+  classifier kinds connected / dropout / softmax / cost / logistic
+  (parseConnected 146-152, parseDropOut 301-331, parseLogistic 714-720,
+  parseSoftmax 722-738, parseCost 740-755).
 * ``load_weights`` / ``write_weights``: the darknet .weights layout read by
   TDarknetParser.loadWeights (nparser.pas:1275-1330): int32 major, minor,
   revision, then ``seen`` as uint64 when major*10+minor >= 2 (else uint32),
   then per convolutional layer biases[n], (scales, rolling_mean,
   rolling_variance)[n] when batch-normalized, weights[n*c*k*k]
-  (loadConvolutionalWeights, nparser.pas:1140-1185).
+  (loadConvolutionalWeights, nparser.pas:1140-1185); per connected layer
+  biases[O], weights[O*I], then (scales, rolling_mean, rolling_variance)[O]
+  when batch-normalized (loadConnectedWeights, nparser.pas:1102-1128).
 * ``fuse_batchnorm``: TBaseConvolutionalLayer.fuseBatchNorm
   (nConvolutionLayer.pas:102-126) in float32: p = scale / sqrt(max(var,
   1e-6)); bias -= mean * p; W *= p.
@@ -73,7 +78,8 @@ def parse_cfg(text: str) -> list[Section]:
 class Layer:
     index: int
     kind: str            # convolutional | shortcut | route | upsample | yolo |
-                         # maxpool | local_avgpool
+                         # maxpool | local_avgpool | connected | dropout |
+                         # softmax | cost | logistic
     c: int               # input channels / height / width
     h: int
     w: int
@@ -91,6 +97,11 @@ class Layer:
     classes: int = 0
     stride_x: int = 0    # pools: the two strides (pad holds their padding);
     stride_y: int = 0    # every other layer: both = stride
+    probability: float = 0.0   # dropout (a float32 value)
+    scale: float = 1.0         # dropout: 1/(1-probability) as float32; cost: scale
+    groups: int = 1            # softmax
+    temperature: float = 1.0
+    noloss: bool = False
 
     def __post_init__(self):
         self.stride_x = self.stride_x or self.stride
@@ -100,9 +111,28 @@ class Layer:
     def out_size(self) -> int:
         return self.out_c * self.out_h * self.out_w
 
+    @property
+    def in_size(self) -> int:
+        return self.c * self.h * self.w
+
 
 def _act(name: str) -> int:
     return ACT[name.strip().upper()]
+
+
+def _flag(sec: Section, key: str) -> bool:
+    """TCFGSection.getBool (nconfig.pas:228-237): val() as an integer, <> 0
+    (text that is no integer reads as 0)."""
+    try:
+        return int(str(sec.get(key, "0")).strip()) != 0
+    except ValueError:
+        return False
+
+
+# kinds that read params.c / h / w, which the reference leaves stale after a
+# layer that is no TBaseImageLayer (nparser.pas:913-919)
+_IMAGE_KINDS = ("convolutional", "conv", "shortcut", "route", "concat", "upsample", "yolo",
+                "maxpool", "max", "local_avgpool")
 
 
 class Network:
@@ -114,8 +144,13 @@ class Network:
         self.h, self.w, self.c = net.int("height"), net.int("width"), net.int("channels", 3)
         self.layers: list[Layer] = []
         c, h, w = self.c, self.h, self.w
+        flat = False  # a [connected] has been planned: c, h, w are the parser's no longer
         for sec in sections[1:]:
             i = len(self.layers)
+            if flat and sec.kind in _IMAGE_KINDS:
+                raise ValueError(f"[{sec.kind}] layer {i} after a [connected] layer: the reference "
+                                 "plans it on the image shape of an earlier layer "
+                                 "(nparser.pas:913-919); refused")
             if sec.kind in ("convolutional", "conv"):
                 size = sec.int("size", 1)
                 stride = sec.int("stride", 1)
@@ -167,6 +202,44 @@ class Network:
                 lay = Layer(i, kind, c, h, w, c, (h + padding - size) // sy + 1,
                             (w + padding - size) // sx + 1, size=size, stride=sx, pad=padding,
                             stride_x=sx, stride_y=sy)
+            elif sec.kind in ("connected", "conn"):
+                o = sec.int("output", 1)
+                if o < 1 or c * h * w < 1:
+                    raise ValueError(f"[connected] layer {i}: {c * h * w} inputs, output={o}")
+                lay = Layer(i, "connected", c, h, w, o, 1, 1, filters=o,
+                            activation=_act(sec.get("activation", "relu")),
+                            bn=_flag(sec, "batch_normalize"))
+                flat = True
+            elif sec.kind == "dropout":
+                # probability is a single; scale := 1 / (1.0 - probability) in
+                # double, stored as single (ndropoutlayer.pas:65)
+                p = np.float32(sec.get("probability", 0.2))
+                if not p < 1:  # the constructor's assert
+                    raise ValueError(f"[dropout] layer {i}: probability {p} must be below one")
+                if _flag(sec, "dropblock"):
+                    raise ValueError(f"[dropout] layer {i}: dropblock is not built (the "
+                                     "reference's device path has none)")
+                lay = Layer(i, "dropout", c, h, w, c, h, w, probability=float(p),
+                            scale=float(np.float32(1.0 / (1.0 - float(p)))))
+            elif sec.kind in ("softmax", "soft"):
+                if sec.get("tree", ""):
+                    raise ValueError(f"[softmax] layer {i}: tree= is not built")
+                g = sec.int("groups", 1)
+                if g < 1 or (c * h * w) % g:
+                    raise ValueError(f"[softmax] layer {i}: {c * h * w} inputs in {g} groups")
+                lay = Layer(i, "softmax", c, h, w, c, h, w, groups=g,
+                            temperature=float(np.float32(sec.get("temperature", 1))),
+                            noloss=_flag(sec, "noloss"))
+            elif sec.kind == "cost":
+                # the reference's device path runs costL2 whatever the type
+                # says (ncostlayer.pas:218-228): only the L2 types are taken
+                ty = str(sec.get("type", "sse")).strip().lower()
+                if ty not in ("sse", "l2"):
+                    raise ValueError(f"[cost] layer {i}: type={ty} is not built (sse / L2 only)")
+                lay = Layer(i, "cost", c, h, w, c, h, w,
+                            scale=float(np.float32(sec.get("scale", 1))))
+            elif sec.kind == "logistic":
+                lay = Layer(i, "logistic", c, h, w, c, h, w, activation=ACT["LOGISTIC"])
             else:
                 raise ValueError(f"[Parser][{sec.kind}] layer is not yet implemented!")
             self.layers.append(lay)
@@ -174,6 +247,11 @@ class Network:
 
     def convs(self) -> list[Layer]:
         return [l for l in self.layers if l.kind == "convolutional"]
+
+    def param_layers(self) -> list[Layer]:
+        """The layers that own parameters, in file order (loadWeights'
+        order, nparser.pas:1309-1325)."""
+        return [l for l in self.layers if l.kind in ("convolutional", "connected")]
 
 
 def yolov3_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
@@ -262,6 +340,54 @@ def yolov3_tiny_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
     return "\n".join(out)
 
 
+def _classifier_cfg(batch: int, size: int, channels: int, body: list[str]) -> str:
+    head = (f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={size}\nheight={size}\n"
+            f"channels={channels}\n")
+    return "\n".join([head, *body])
+
+
+def _cconv(f, k, padding, bn):
+    return (f"[convolutional]\n{'batch_normalize=1' + chr(10) if bn else ''}filters={f}\n"
+            f"size={k}\nstride=1\npadding={padding}\nactivation=relu\n")
+
+
+_CPOOL = "[maxpool]\nsize=2\nstride=2\npadding=0\n"
+
+
+def _cfc(o, act):
+    return f"[connected]\noutput={o}\nactivation={act}\n"
+
+
+def cifar10_deep_cfg(batch: int = 1) -> str:
+    """deepCIFAR10 (nmodels.pas:82-108): three stages of two batch-normalised
+    3x3 convolutions and a 2x2 max pool, then dropout 0.2, connected 1024
+    (relu), dropout 0.2, connected 10 (linear), softmax."""
+    body = []
+    for f in (32, 64, 128):
+        body += [_cconv(f, 3, 1, True), _cconv(f, 3, 1, True), _CPOOL]
+    body += ["[dropout]\nprobability=0.2\n", _cfc(1024, "relu"), "[dropout]\nprobability=0.2\n",
+             _cfc(10, "linear"), "[softmax]\n"]
+    return _classifier_cfg(batch, 32, 3, body)
+
+
+def lenet_cifar10_cfg(batch: int = 1) -> str:
+    """leNetCIFAR10 (nmodels.pas:66-80): batch-normalised 5x5 convolutions
+    (6, 12, 120 filters, no padding) with two 2x2 max pools, connected 84
+    (relu), connected 10 (linear), softmax."""
+    body = [_cconv(6, 5, 0, True), _CPOOL, _cconv(12, 5, 0, True), _CPOOL, _cconv(120, 5, 0, True),
+            _cfc(84, "relu"), _cfc(10, "linear"), "[softmax]\n"]
+    return _classifier_cfg(batch, 32, 3, body)
+
+
+def lenet_mnist_cfg(batch: int = 1) -> str:
+    """leNetMNIST (nmodels.pas:50-64): 5x5 convolutions without batch norm
+    (6 filters at padding 2, then 16 and 120 at padding 0) with two 2x2 max
+    pools, connected 84 (relu), connected 10 (linear), softmax."""
+    body = [_cconv(6, 5, 2, False), _CPOOL, _cconv(16, 5, 0, False), _CPOOL,
+            _cconv(120, 5, 0, False), _cfc(84, "relu"), _cfc(10, "linear"), "[softmax]\n"]
+    return _classifier_cfg(batch, 28, 1, body)
+
+
 # ---- parameters -------------------------------------------------------------
 
 @dataclass
@@ -274,11 +400,22 @@ class ConvParams:
 
 
 def random_params(net: Network, seed: int = 3) -> list[ConvParams]:
-    """Synthetic parameters of the reference's initialisation scale
-    (nConvolutionLayer.pas:216-220: U[-s, s], s = sqrt(2/(k*k*c)))."""
+    """Synthetic parameters, one entry per convolutional or connected layer in
+    file order.  Convolutions: the reference's initialisation scale
+    (nConvolutionLayer.pas:216-220: U[-s, s], s = sqrt(2/(k*k*c))).  Connected
+    layers: TConnectedLayer.Create (nconnectedlayer.pas:78-99): weights
+    [outputs][inputs] U[-s, s] with s = single(sqrt(2/inputs)), biases 0,
+    scales 1 and rolling statistics 0 when batch-normalised."""
     rng = np.random.default_rng(seed)
     ps = []
-    for l in net.convs():
+    for l in net.param_layers():
+        if l.kind == "connected":
+            s = float(np.float32(np.sqrt(2.0 / l.in_size)))
+            w = rng.uniform(-s, s, (l.filters, l.in_size)).astype(np.float32)
+            z = lambda: np.zeros(l.filters, np.float32)  # noqa: E731
+            ps.append(ConvParams(z(), w, np.ones(l.filters, np.float32), z(), z()) if l.bn
+                      else ConvParams(z(), w))
+            continue
         s = np.sqrt(2.0 / (l.size * l.size * l.c))
         w = rng.uniform(-s, s, (l.filters, l.c * l.size * l.size)).astype(np.float32)
         b = rng.uniform(-0.1, 0.1, l.filters).astype(np.float32)
@@ -291,23 +428,35 @@ def random_params(net: Network, seed: int = 3) -> list[ConvParams]:
     return ps
 
 
+def _no_transpose(major, minor):
+    if major > 1000 or minor > 1000:  # loadWeights' transpose flag (nparser.pas:1307)
+        raise ValueError("weights file with the transpose flag (major or minor > 1000) is "
+                         "not supported")
+
+
 def write_weights(path, net: Network, params: list[ConvParams], major=0, minor=2, revision=0,
                   seen=0) -> None:
+    _no_transpose(major, minor)
     with open(path, "wb") as f:
         f.write(struct.pack("<3i", major, minor, revision))
         f.write(struct.pack("<Q" if major * 10 + minor >= 2 else "<I", seen))
-        for l, p in zip(net.convs(), params):
+        for l, p in zip(net.param_layers(), params):
             f.write(p.biases.astype("<f4").tobytes())
+            if l.kind == "connected":  # weights before the batch-norm arrays
+                f.write(p.weights.astype("<f4").tobytes())
             if l.bn:
                 for t in (p.scales, p.rolling_mean, p.rolling_var):
                     f.write(t.astype("<f4").tobytes())
-            f.write(p.weights.astype("<f4").tobytes())
+            if l.kind == "convolutional":
+                f.write(p.weights.astype("<f4").tobytes())
 
 
 def load_weights(path, net: Network) -> tuple[list[ConvParams], int]:
-    """Returns the per-conv parameters and ``seen``."""
+    """Returns the per-layer parameters (convolutional and connected layers
+    in file order) and ``seen``."""
     data = Path(path).read_bytes()
     major, minor, _rev = struct.unpack_from("<3i", data, 0)
+    _no_transpose(major, minor)
     off = 12
     if major * 10 + minor >= 2:
         (seen,) = struct.unpack_from("<Q", data, off)
@@ -325,12 +474,17 @@ def load_weights(path, net: Network) -> tuple[list[ConvParams], int]:
         return a
 
     ps = []
-    for l in net.convs():
+    for l in net.param_layers():
         b = take(l.filters)
         sc = rm = rv = None
-        if l.bn:
-            sc, rm, rv = take(l.filters), take(l.filters), take(l.filters)
-        w = take(l.filters * l.c * l.size * l.size).reshape(l.filters, -1)
+        if l.kind == "connected":
+            w = take(l.filters * l.in_size).reshape(l.filters, -1)
+            if l.bn:
+                sc, rm, rv = take(l.filters), take(l.filters), take(l.filters)
+        else:
+            if l.bn:
+                sc, rm, rv = take(l.filters), take(l.filters), take(l.filters)
+            w = take(l.filters * l.c * l.size * l.size).reshape(l.filters, -1)
         ps.append(ConvParams(b, w, sc, rm, rv))
     return ps, seen
 
@@ -349,18 +503,32 @@ class HipDarknet:
     """TNNet.forward over a darknet layer plan on the HIP backend (nnet.pas:
     275-310 selects forwardGPU per layer): every layer's output stays in a
     device buffer of its own; convolutions take BN-folded parameters
-    (fuseBatchNorm) and run the fused implicit-GEMM driver."""
+    (fuseBatchNorm) and run the fused implicit-GEMM driver.  Connected layers
+    run TConnectedLayer.forwardGPU's inference branch (nconnectedlayer.pas:
+    640-733: NT gemm, normalize by the rolling statistics + forwardScaleAdd,
+    or forwardBias, then ActivateArray).  A dropout layer's output is its
+    input buffer and nothing runs (ndropoutlayer.pas:156-161); softmax is
+    softmaxBatch, logistic copy + ActivateArray, cost nothing (no truth)."""
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch):
         self.hip, self.net, self.torch = hip, net, torch
         B = net.batch
         dev = "cuda"
-        self.out = [torch.empty(B * l.out_size, device=dev) for l in net.layers]
-        self.conv_params = {}
-        for l, p in zip(net.convs(), params):
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+        self.out = []
+        for l in net.layers:  # (a dropout at layer 0 takes the input in forward)
+            alias = l.kind == "dropout" and l.index > 0
+            self.out.append(self.out[-1] if alias else torch.empty(B * l.out_size, device=dev))
+        self.conv_params, self.fc_params = {}, {}
+        for l, p in zip(net.param_layers(), params):
+            if l.kind == "connected":
+                st = {"w": t(p.weights), "b": t(p.biases)}
+                if l.bn:
+                    st.update(scales=t(p.scales), rm=t(p.rolling_mean), rv=t(p.rolling_var))
+                self.fc_params[l.index] = st
+                continue
             f = fuse_batchnorm(l, p)
-            self.conv_params[l.index] = (torch.from_numpy(np.ascontiguousarray(f.weights)).to(dev),
-                                         torch.from_numpy(np.ascontiguousarray(f.biases)).to(dev))
+            self.conv_params[l.index] = (t(f.weights), t(f.biases))
 
     def forward(self, x):
         """x: device tensor [batch, c, h, w] (contiguous).  Returns the per-
@@ -392,6 +560,24 @@ class HipDarknet:
             elif l.kind == "local_avgpool":
                 hip.forwardAvgPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
                                    l.stride_y, l.pad, l.size, out)
+            elif l.kind == "connected":
+                st, n = self.fc_params[l.index], B * l.filters
+                hip.gemm(False, True, B, l.filters, l.in_size, 1.0, prev, 0, l.in_size, st["w"], 0,
+                         l.in_size, 0.0, out, 0, l.filters)
+                if l.bn:
+                    hip.normalize(l.filters, n, B, st["rm"], 1, st["rv"], 1, out, 0)
+                    hip.forwardScaleAdd(n, out, 0, l.filters, st["scales"], st["b"], 1, B)
+                else:
+                    hip.forwardBias(n, out, 0, l.filters, st["b"], 1, B)
+                hip.ActivateArray(n, out, 0, l.activation)
+            elif l.kind == "dropout":
+                out = self.out[l.index] = prev.reshape(-1)
+            elif l.kind == "softmax":
+                g = l.in_size // l.groups
+                hip.softmaxBatch(g, prev, 0, B, l.in_size, l.groups, g, 1, l.temperature, out, 0)
+            elif l.kind == "logistic":
+                hip.copy(B * l.in_size, prev, 0, 1, out, 0, 1)
+                hip.ActivateArray(B * l.in_size, out, 0, l.activation)
             prev = out
         return self.out
 
@@ -422,27 +608,65 @@ class HipDarknetTrain:
     * maxpool / local_avgpool (TMaxPoolLayer.backwardGPU, nMaxPoolLayer.pas:
       689-706; CPU loops 501-542): ``backwardMaxPool`` with the indexes its
       forward stored, or ``backwardAvgPool``, accumulating into state.delta;
-      nothing when the pool is layer 0 (no state.delta).
+      nothing when the pool is layer 0 (no state.delta);
+    * connected (TConnectedLayer.forwardGPU / backwardGPU, nconnectedlayer.pas:
+      612-871): NT ``gemm``; with batch norm ``means``, ``variances``, the
+      rolling statistics by ``scale`` / ``axpy`` (bnMomentum 0.05, line 67),
+      ``copy`` to x, ``normalize``, ``copy`` to x_norm, ``forwardScaleAdd``,
+      otherwise ``forwardBias``; ``ActivateArray``.  Backward: ``clamp(delta,
+      1)``, ``DeriveArray``, ``backwardBias``, with batch norm ``addDots``,
+      ``forwardScale``, ``meansAndVarsDelta``, ``normalizeDelta``, then the
+      TN ``gemm`` into weight_updates and the NN ``gemm`` into state.delta;
+    * dropout (ndropoutlayer.pas:156-172): ``output := state.input^`` — the
+      layer's output buffer IS the layer below's, so ``forwardDropout`` runs
+      in place on it (the layer below derives its activation from the dropped,
+      scaled output) with the layer's rnd buffer; ``backwardDropout`` in place
+      on state.delta, which the layer's delta aliases.  (The reference assigns
+      that alias only at the end of the first backward, so its first step
+      passes no gradient below a dropout layer; here the alias holds from the
+      start);
+    * softmax (nsoftmaxlayer.pas:279-341): ``softmaxBatch``; with truth and
+      not noloss ``crossEntropySoftmax`` and cost = ``sum(loss)`` (vssum
+      order); backward ``addvv`` of its delta into state.delta;
+    * cost (ncostlayer.pas:218-228): ``costL2``, cost = ``sum(output)``;
+      backward ``axpy(scale, delta, state.delta)``;
+    * logistic (nlogisticlayer.pas:181-): ``copy``, ``ActivateArray``,
+      ``crossEntropyLogistic``, cost = ``sum(loss)``; backward ``addvv``.
 
     Convolutions with batch norm run ``convForwardTrain`` (training-time BN,
-    nbaselayer.pas:336-370) in the forward, the heads ``convForward``.  No
-    weight update is made here (TNet.update is a separate call per layer,
-    ``sgdUpdate``)."""
+    nbaselayer.pas:336-370) in the forward, the heads ``convForward``.
+    ``update`` is TNNet.update (nnet.pas:371-403): ``sgdUpdate`` per layer."""
 
-    def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0):
+    LOSS_KINDS = ("softmax", "cost", "logistic")
+
+    def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
+                 seed: int = 0):
         self.hip, self.net, self.torch = hip, net, torch
         self.loss_scale = float(loss_scale)
+        self.rng = np.random.default_rng(seed)  # default dropout seeds
         B = net.batch
         dev = "cuda"
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
-        self.out = [torch.zeros(B * l.out_size, device=dev) for l in net.layers]
-        self.delta = [torch.zeros(B * l.out_size, device=dev) for l in net.layers]
+        self.out, self.delta = [], []
+        for l in net.layers:  # a dropout's output and delta are the layer below's
+            alias = l.kind == "dropout" and l.index > 0
+            self.out.append(self.out[-1] if alias else torch.zeros(B * l.out_size, device=dev))
+            self.delta.append(self.delta[-1] if alias
+                              else torch.zeros(B * l.out_size, device=dev))
+        self.rnd = {l.index: torch.zeros(B * l.out_size, device=dev)
+                    for l in net.layers if l.kind == "dropout"}
+        # softmax / logistic: loss[batch*inputs]; every loss layer: cost[1]
+        self.loss = {l.index: torch.zeros(B * l.out_size, device=dev)
+                     for l in net.layers if l.kind in ("softmax", "logistic")}
+        self.costs = {l.index: torch.zeros(1, device=dev)
+                      for l in net.layers if l.kind in self.LOSS_KINDS}
+        self.fc = {}
         # a maxpool's indexes (TSizeIntTensor, int64): filled by its forward
         self.indexes = {l.index: torch.zeros(B * l.out_size, dtype=torch.int64, device=dev)
                         for l in net.layers if l.kind == "maxpool"}
         self.conv = {}
         ws = 1
-        for l, p in zip(net.convs(), params):
+        for l, p in zip(net.param_layers(), params):
             n = B * l.out_size
             st = {"w": t(p.weights), "b": t(p.biases),
                   "wu": torch.zeros(p.weights.size, device=dev),
@@ -455,16 +679,41 @@ class HipDarknetTrain:
                           su=torch.zeros(l.filters, device=dev),
                           md=torch.zeros(l.filters, device=dev),
                           vd=torch.zeros(l.filters, device=dev))
+            if l.kind == "connected":
+                self.fc[l.index] = st
+                continue
             self.conv[l.index] = st
             ws = max(ws, B * l.c * l.size * l.size * l.out_h * l.out_w)
         self.ws = torch.empty(ws, device=dev)
 
-    def forward(self, x):
+    def forward(self, x, truth=None, seeds=None):
         """TNet.forward with state.isTraining (BN statistics of the batch,
-        rolling statistics updated with bnMomentum 0.1)."""
+        rolling statistics updated with bnMomentum 0.1, connected layers
+        0.05).  truth: device tensor of the loss layers' size (state.truth),
+        or None (no loss is computed).  seeds: one integer in [0, 2^32) per
+        dropout layer, in layer order; by default drawn in [0, 2^28), the
+        reference's random($10000000), from the generator seeded at
+        construction."""
         hip, B = self.hip, self.net.batch
+        drops = [l for l in self.net.layers if l.kind == "dropout"]
+        if seeds is None:
+            seeds = [int(self.rng.integers(0, 1 << 28)) for _ in drops]
+        if len(seeds) != len(drops):
+            raise ValueError(f"{len(seeds)} seeds for {len(drops)} dropout layers")
+        seeds = dict(zip((l.index for l in drops), seeds))
+        if truth is not None:
+            truth = truth.reshape(-1)
         prev = x
         for l in self.net.layers:
+            if l.kind == "dropout":  # its delta is the layer below's, zeroed there
+                n = B * l.out_size
+                if l.index == 0:
+                    self.out[0] = prev.reshape(-1)
+                out = self.out[l.index]
+                hip.forwardDropout(n, out, l.probability, l.scale, self.rnd[l.index], out,
+                                   seeds[l.index])
+                prev = out
+                continue
             hip.scale(self.delta[l.index].numel(), 0.0, self.delta[l.index], 1)
             out = self.out[l.index]
             if l.kind == "convolutional":
@@ -496,8 +745,90 @@ class HipDarknetTrain:
             elif l.kind == "local_avgpool":
                 hip.forwardAvgPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
                                    l.stride_y, l.pad, l.size, out)
+            elif l.kind == "connected":
+                self._fc_forward(l, prev, out)
+            elif l.kind == "softmax":
+                n, g = B * l.in_size, l.in_size // l.groups
+                hip.softmaxBatch(g, prev, 0, B, l.in_size, l.groups, g, 1, l.temperature, out, 0)
+                if truth is not None and not l.noloss:
+                    hip.crossEntropySoftmax(n, out, truth, self.delta[l.index], self.loss[l.index])
+                    hip.sum(n, self.loss[l.index], 0, self.costs[l.index])
+            elif l.kind == "cost":
+                if truth is not None:
+                    n = B * l.in_size
+                    hip.costL2(n, prev, truth, self.delta[l.index], out)
+                    hip.sum(n, out, 0, self.costs[l.index])
+            elif l.kind == "logistic":
+                n = B * l.in_size
+                hip.copy(n, prev, 0, 1, out, 0, 1)
+                hip.ActivateArray(n, out, 0, l.activation)
+                if truth is not None:
+                    hip.crossEntropyLogistic(n, out, truth, self.delta[l.index],
+                                             self.loss[l.index])
+                    hip.sum(n, self.loss[l.index], 0, self.costs[l.index])
             prev = out
         return self.out
+
+    def _fc_forward(self, l, prev, out):
+        hip, B, st = self.hip, self.net.batch, self.fc[l.index]
+        O, I = l.filters, l.in_size
+        n = B * O
+        hip.gemm(False, True, B, O, I, 1.0, prev, 0, I, st["w"], 0, I, 0.0, out, 0, O)
+        if l.bn:
+            mom = np.float32(0.05)  # bnMomentum (nconnectedlayer.pas:67), single arithmetic
+            keep = float(np.float32(1) - mom)
+            hip.means(n, O, B, out, 0, st["mean"])
+            hip.variances(n, O, B, out, 0, st["mean"], st["var"])
+            hip.scale(O, keep, st["rm"], 1)
+            hip.axpy(O, float(mom), st["mean"], 0, 1, st["rm"], 0, 1)
+            hip.scale(O, keep, st["rv"], 1)
+            hip.axpy(O, float(mom), st["var"], 0, 1, st["rv"], 0, 1)
+            hip.copy(n, out, 0, 1, st["x"], 0, 1)
+            hip.normalize(O, n, B, st["mean"], 1, st["var"], 1, out, 0)
+            hip.copy(n, out, 0, 1, st["xn"], 0, 1)
+            hip.forwardScaleAdd(n, out, 0, O, st["scales"], st["b"], 1, B)
+        else:
+            hip.forwardBias(n, out, 0, O, st["b"], 1, B)
+        hip.ActivateArray(n, out, 0, l.activation)
+
+    def _fc_backward(self, l, inp, sd):
+        hip, B, st = self.hip, self.net.batch, self.fc[l.index]
+        O, I = l.filters, l.in_size
+        n, d = B * O, self.delta[l.index]
+        hip.clamp(n, 1.0, d, d)
+        hip.DeriveArray(n, self.out[l.index], 0, l.activation, d)
+        hip.backwardBias(O, st["bu"], n, d, 0, 1, B)
+        if l.bn:
+            hip.addDots(n, O, B, st["xn"], d, 0, st["su"])
+            hip.forwardScale(n, d, 0, O, st["scales"], 1, B)
+            hip.meansAndVarsDelta(n, O, B, d, st["x"], 0, st["mean"], st["var"], st["md"],
+                                  st["vd"])
+            hip.normalizeDelta(n, O, B, d, st["x"], 0, st["mean"], st["var"], st["md"], st["vd"])
+        hip.gemm(True, False, O, I, B, 1.0, d, 0, O, inp, 0, I, 1.0, st["wu"], 0, I)
+        if sd is not None:
+            hip.gemm(False, False, B, I, O, 1.0, d, 0, O, st["w"], 0, I, 1.0, sd, 0, I)
+
+    def cost(self) -> float:
+        """TNNet.cost (nnet.pas:551-564): the loss layers' cost[0] summed and
+        divided by their count, in single arithmetic."""
+        if not self.costs:
+            raise ValueError("the network has no loss layer")
+        r = np.float32(0)
+        for i in sorted(self.costs):
+            r = np.float32(r + np.float32(self.costs[i].item()))
+        return float(np.float32(r / np.float32(len(self.costs))))
+
+    def update(self, learning_rate, momentum, decay):
+        """TNNet.update (nnet.pas:371-403) at a constant learning rate:
+        ``sgdUpdate`` (updateGPU's axpy / scale sequence fused) on every
+        convolutional and connected layer of layers 0 .. n-2 — the reference's
+        loop stops before the last layer — with args.batch = net.batch."""
+        for l in self.net.layers[:-1]:
+            st = self.conv.get(l.index) or self.fc.get(l.index)
+            if st is None:
+                continue
+            self.hip.sgdUpdate(st["w"], st["wu"], st["b"], st["bu"], learning_rate, self.net.batch,
+                               decay, momentum, st.get("scales"), st.get("su"))
 
     def set_yolo_deltas(self, deltas):
         """The yolo layers' deltas (what their training forward's loss would
@@ -548,5 +879,13 @@ class HipDarknetTrain:
             elif l.kind == "local_avgpool" and sd is not None:
                 hip.backwardAvgPool(B, l.out_c, l.out_h, l.out_w, sd, d, l.h, l.w, l.stride_x,
                                     l.stride_y, l.pad, l.size)
+            elif l.kind == "connected":
+                self._fc_backward(l, inp.reshape(-1), sd)
+            elif l.kind == "dropout" and sd is not None:
+                hip.backwardDropout(sd.numel(), sd, l.probability, l.scale, self.rnd[i], sd)
+            elif l.kind in ("softmax", "logistic") and sd is not None:
+                hip.addvv(d.numel(), d, 0, 1, sd, 0, 1, sd, 0, 1)
+            elif l.kind == "cost" and sd is not None:
+                hip.axpy(d.numel(), l.scale, d, 0, 1, sd, 0, 1)
             if on_backward is not None:
                 on_backward(l)

@@ -537,6 +537,26 @@ class TNNHip:
         check(self.lib.tns_hip_cross_entropy_softmax(self.ctx, N, _ptr(pred), _ptr(truth),
                                                      _ptr(delta), _ptr(error)))
 
+    # -- dropout and the elementwise loss heads -----------------------------------
+    def forwardDropout(self, N, src, probability, scale, rnd, dst, seed):
+        """TNNCuda.forwardDropout (nncuda.pas:1510-1530) with the seed the
+        reference draws inside (random($10000000)) as an argument: rnd[i] is a
+        pure function of (seed, i); src may be dst."""
+        check(self.lib.tns_hip_dropout_forward(self.ctx, N, int(seed), float(probability),
+                                               float(scale), _ptr(src), _ptr(rnd), _ptr(dst)))
+
+    def backwardDropout(self, N, src, probability, scale, rnd, dst):
+        check(self.lib.tns_hip_dropout_backward(self.ctx, N, float(probability), float(scale),
+                                                _ptr(src), _ptr(rnd), _ptr(dst)))
+
+    def costL2(self, N, pred, truth, delta, error):
+        check(self.lib.tns_hip_cost_l2(self.ctx, N, _ptr(pred), _ptr(truth), _ptr(delta),
+                                       _ptr(error)))
+
+    def crossEntropyLogistic(self, N, pred, truth, delta, error):
+        check(self.lib.tns_hip_cross_entropy_logistic(self.ctx, N, _ptr(pred), _ptr(truth),
+                                                      _ptr(delta), _ptr(error)))
+
     def sum(self, N, src, offset, out):
         check(self.lib.tns_hip_sum(self.ctx, N, _ptr(src), offset, _ptr(out)))
 
