@@ -395,6 +395,45 @@ int tns_hip_cost_l2(tns_ctx* ctx, int64_t N, const float* pred, const float* tru
 int tns_hip_cross_entropy_logistic(tns_ctx* ctx, int64_t N, const float* pred,
                                    const float* truth, float* delta, float* error);
 
+/* ---- the gate stage of one LSTM time step (lstm.hip) ----
+ * Backend-specific fused entries (TNNCuda has none): what
+ * TLSTMLayer.forwardGPU / backwardGPU (nlstmlayer.pas:933-973, 1046-1255)
+ * issue as addvv / ActivateArray / mulvv / fmavv / copy / DeriveArray calls
+ * around the eight connected sub-layers, per element k of the step's N =
+ * streams * outputs floats.  w_x / u_x are the step's slice of the sub-layers'
+ * output; a_x = w_x[k] + u_x[k].  Every written operation is one float32
+ * rounding; logistic = 1/(1+exp(-x)) in double rounded once, tanh =
+ * (px-nx)/(px+nx) on the single-rounded exponentials.
+ * tns_hip_lstm_gates_forward:
+ *   f = logistic(a_f)  i = logistic(a_i)  g = tanh(a_g)  o = logistic(a_o)
+ *   t = i*g;  c = c_state[k]*f;  c = c + t;  h = tanh(c)*o
+ *   c -> c_state[k], cell_slice[k];  h -> h_state[k], out_slice[k]
+ * tns_hip_lstm_gates_backward (f, i, g, o as above):
+ *   t = tanh(cell_i[k]);  d = delta_i[k]
+ *   e = d*o;  e = e*(1 - t*t);  e = dc[k] + e
+ *   do = (d*t)*((1-o)*o)      dg = (e*i)*(1 - g*g)
+ *   di = (e*g)*((1-i)*i)      df = (e*cprev[k])*((1-f)*f)
+ *   dc[k] = e*f
+ * Each gate delta is stored clamped to [-1, 1] (v < -1 ? -1 : v > 1 ? 1 : v;
+ * a NaN stays) — the clamp(delta, 1) that opens the sub-layer's backwardGPU
+ * (nconnectedlayer.pas:771) — to the w-side slice dw_x and, where du_x is not
+ * null, to the u-side slice.  dc is not clamped.  c_state and dc are read and
+ * written in place.  TNS_ERR_ARG, before any launch and with every output
+ * untouched: N < 0, a null operand with N > 0 (du_x excepted), an output
+ * (c_state, h_state, cell_slice, out_slice; dc, dw_x, du_x) overlapping any
+ * other operand.  Inputs may overlap one another.  N == 0 does nothing. */
+int tns_hip_lstm_gates_forward(tns_ctx* ctx, int64_t N, const float* wf, const float* wi,
+                               const float* wg, const float* wo, const float* uf,
+                               const float* ui, const float* ug, const float* uo,
+                               float* c_state, float* h_state, float* cell_slice,
+                               float* out_slice);
+int tns_hip_lstm_gates_backward(tns_ctx* ctx, int64_t N, const float* wf, const float* wi,
+                                const float* wg, const float* wo, const float* uf,
+                                const float* ui, const float* ug, const float* uo,
+                                const float* cell_i, const float* cprev, const float* delta_i,
+                                float* dc, float* dwf, float* dwi, float* dwg, float* dwo,
+                                float* duf, float* dui, float* dug, float* duo);
+
 /* ---- batch norm / softmax (TNNCuda twins, nncuda.pas:1056-1510; CPU
  * semantics ntensors.pas:7687-7830, 8693-8951, 9102-9177,
  * nsoftmaxlayer.pas:83-137).  Data is [groups][channels][blockSize]. ---- */

@@ -213,6 +213,14 @@ function tns_hip_cost_l2(ctx: PTnsCtx; N: int64; pred, truth, delta, error: THip
 function tns_hip_cross_entropy_logistic(ctx: PTnsCtx; N: int64; pred, truth, delta,
   error: THipMem): longint; cdecl; external libtns;
 
+{ the gate stage of one LSTM time step (lstm.hip): w / u the step's slices of
+  the sub-layers' outputs; c_state and dc in / out; a du may be nil }
+function tns_hip_lstm_gates_forward(ctx: PTnsCtx; N: int64; wf, wi, wg, wo, uf, ui, ug, uo,
+  c_state, h_state, cell_slice, out_slice: THipMem): longint; cdecl; external libtns;
+function tns_hip_lstm_gates_backward(ctx: PTnsCtx; N: int64; wf, wi, wg, wo, uf, ui, ug, uo,
+  cell_i, cprev, delta_i, dc, dwf, dwi, dwg, dwo, duf, dui, dug, duo: THipMem): longint;
+  cdecl; external libtns;
+
 { batch norm / softmax }
 function tns_hip_means_and_vars(ctx: PTnsCtx; srcSize, dstSize, groups: int64; src: THipMem;
   offset: int64; means, vars: THipMem): longint; cdecl; external libtns;
@@ -384,6 +392,10 @@ type
     procedure convForward(const batch, C, H, W: SizeInt; const input, weights, biases: TCUMem; const filters, kSize, stride, padding, dilation: SizeInt; const activation: longint; const workspace, output: TCUMem; const fused: longint = TNS_CONV_FUSED);
     procedure convBackward(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding, dilation: SizeInt; const activation: longint; const output, delta, bias_updates, weight_updates, workspace, state_delta: TCUMem);
     procedure sgdUpdate(const nWeights: SizeInt; const weights, weight_updates: TCUMem; const n: SizeInt; const biases, bias_updates, scales, scale_updates: TCUMem; const learningRate: T; const batch: SizeInt; const momentum, decay: T);
+    { the elementwise calls of one step of TLSTMLayer.forwardGPU / backwardGPU fused
+      (INTEGRATION.md); the offsets are in elements, as everywhere }
+    procedure lstmGatesForward(const N: SizeInt; const wf, wi, wg, wo, uf, ui, ug, uo: TCUMem; const offset: SizeInt; const c_state, h_state, cell, output: TCUMem);
+    procedure lstmGatesBackward(const N: SizeInt; const wf, wi, wg, wo, uf, ui, ug, uo: TCUMem; const offset: SizeInt; const cell, cprev: TCUMem; const cprevOffset: SizeInt; const delta, dc, dwf, dwi, dwg, dwo, duf, dui, dug, duo: TCUMem);
 
     property ctx: PTnsCtx read FCtx;
   end;
@@ -727,6 +739,26 @@ end;
 procedure TNNHip<T>.costL2(const N: SizeInt; const pred, truth, delta, error: TCUMem);
 begin
   check(tns_hip_cost_l2(FCtx, N, THipMem(pred), THipMem(truth), THipMem(delta), THipMem(error)))
+end;
+
+procedure TNNHip<T>.lstmGatesForward(const N: SizeInt; const wf, wi, wg, wo, uf, ui, ug, uo: TCUMem; const offset: SizeInt; const c_state, h_state, cell, output: TCUMem);
+begin
+  check(tns_hip_lstm_gates_forward(FCtx, N, THipMem(wf) + offset, THipMem(wi) + offset,
+    THipMem(wg) + offset, THipMem(wo) + offset, THipMem(uf) + offset, THipMem(ui) + offset,
+    THipMem(ug) + offset, THipMem(uo) + offset, THipMem(c_state), THipMem(h_state),
+    THipMem(cell) + offset, THipMem(output) + offset))
+end;
+
+procedure TNNHip<T>.lstmGatesBackward(const N: SizeInt; const wf, wi, wg, wo, uf, ui, ug, uo: TCUMem; const offset: SizeInt; const cell, cprev: TCUMem; const cprevOffset: SizeInt; const delta, dc, dwf, dwi, dwg, dwo, duf, dui, dug, duo: TCUMem);
+  function at(const p: TCUMem): THipMem;
+  begin
+    if p = nil then exit(nil);
+    result := THipMem(p) + offset
+  end;
+begin
+  check(tns_hip_lstm_gates_backward(FCtx, N, at(wf), at(wi), at(wg), at(wo), at(uf), at(ui),
+    at(ug), at(uo), at(cell), THipMem(cprev) + cprevOffset, at(delta), THipMem(dc), at(dwf),
+    at(dwi), at(dwg), at(dwo), at(duf), at(dui), at(dug), at(duo)))
 end;
 
 procedure TNNHip<T>.clamp(const N: SizeInt; const alpha: T; const src, dst: TCUMem; const stride: SizeInt; offset: SizeInt);

@@ -214,6 +214,9 @@ PROTOTYPES.update({
     "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),
     "tns_hip_cost_l2": (C.c_int, [vp, i64, fptr, fptr, fptr, fptr]),
     "tns_hip_cross_entropy_logistic": (C.c_int, [vp, i64, fptr, fptr, fptr, fptr]),
+    # the LSTM gate stage: 8 pre-activation slices, then the state / slices
+    "tns_hip_lstm_gates_forward": (C.c_int, [vp, i64] + [fptr] * 12),
+    "tns_hip_lstm_gates_backward": (C.c_int, [vp, i64] + [fptr] * 20),
     "tns_hip_means_and_vars": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),
     "tns_hip_means": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr]),
     "tns_hip_variances": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),

@@ -1450,6 +1450,89 @@ int tns_hip_cross_entropy_logistic(tns_ctx* c, int64_t N, const float* pred, con
                     "crossEntropyLogistic");
 }
 
+namespace {
+
+// the LSTM gate entries: no output may meet any other operand (an in / out
+// operand is one operand); inputs may meet one another
+static int lstm_operands(const char* what, int64_t N, std::initializer_list<const float*> in,
+                  std::initializer_list<const float*> out,
+                  std::initializer_list<const float*> optional_out) {
+  if (N < 0) return set_error(TNS_ERR_ARG, "%s: N = %lld", what, (long long)N);
+  if (N == 0) return TNS_OK;
+  for (const float* p : in)
+    if (!p) return set_error(TNS_ERR_ARG, "%s: null operand", what);
+  for (const float* p : out)
+    if (!p) return set_error(TNS_ERR_ARG, "%s: null operand", what);
+  const uintptr_t len = (uintptr_t)N * sizeof(float);
+  auto meet = [len](const float* a, const float* b) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + len && y < x + len;
+  };
+  std::vector<const float*> outs(out);
+  outs.insert(outs.end(), optional_out.begin(), optional_out.end());
+  for (size_t a = 0; a < outs.size(); ++a) {
+    for (size_t b = a + 1; b < outs.size(); ++b)
+      if (meet(outs[a], outs[b]))
+        return set_error(TNS_ERR_ARG, "%s: two outputs overlap", what);
+    for (const float* p : in)
+      if (meet(outs[a], p))
+        return set_error(TNS_ERR_ARG, "%s: an output overlaps an input", what);
+  }
+  return TNS_OK;
+}
+
+}  // namespace
+
+int tns_hip_lstm_gates_forward(tns_ctx* c, int64_t N, const float* wf, const float* wi,
+                               const float* wg, const float* wo, const float* uf,
+                               const float* ui, const float* ug, const float* uo, float* c_state,
+                               float* h_state, float* cell_slice, float* out_slice) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (int r = lstm_operands("lstmGatesForward", N, {wf, wi, wg, wo, uf, ui, ug, uo},
+                            {c_state, h_state, cell_slice, out_slice}, {}))
+    return r;
+  if (N == 0) return TNS_OK;
+  if (int r = check_ops(c,
+                        {span(c_state, N), span(h_state, N), span(cell_slice, N),
+                         span(out_slice, N)},
+                        {span(wf, N), span(wi, N), span(wg, N), span(wo, N), span(uf, N),
+                         span(ui, N), span(ug, N), span(uo, N)}))
+    return r;
+  const float* const w[4] = {wf, wi, wg, wo};
+  const float* const u[4] = {uf, ui, ug, uo};
+  return hip_status(
+      launch_lstm_gates_forward(N, w, u, c_state, h_state, cell_slice, out_slice, c->stream),
+      "lstmGatesForward");
+}
+
+int tns_hip_lstm_gates_backward(tns_ctx* c, int64_t N, const float* wf, const float* wi,
+                                const float* wg, const float* wo, const float* uf,
+                                const float* ui, const float* ug, const float* uo,
+                                const float* cell_i, const float* cprev, const float* delta_i,
+                                float* dc, float* dwf, float* dwi, float* dwg, float* dwo,
+                                float* duf, float* dui, float* dug, float* duo) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (int r = lstm_operands("lstmGatesBackward", N,
+                            {wf, wi, wg, wo, uf, ui, ug, uo, cell_i, cprev, delta_i},
+                            {dc, dwf, dwi, dwg, dwo}, {duf, dui, dug, duo}))
+    return r;
+  if (N == 0) return TNS_OK;
+  if (int r = check_ops(c,
+                        {span(dc, N), span(dwf, N), span(dwi, N), span(dwg, N), span(dwo, N),
+                         span(duf, N), span(dui, N), span(dug, N), span(duo, N)},
+                        {span(wf, N), span(wi, N), span(wg, N), span(wo, N), span(uf, N),
+                         span(ui, N), span(ug, N), span(uo, N), span(cell_i, N), span(cprev, N),
+                         span(delta_i, N)}))
+    return r;
+  const float* const w[4] = {wf, wi, wg, wo};
+  const float* const u[4] = {uf, ui, ug, uo};
+  float* const dw[4] = {dwf, dwi, dwg, dwo};
+  float* const du[4] = {duf, dui, dug, duo};
+  return hip_status(launch_lstm_gates_backward(N, w, u, cell_i, cprev, delta_i, dc, dw, du,
+                                               c->stream),
+                    "lstmGatesBackward");
+}
+
 int tns_hip_clamp(tns_ctx* c, int64_t N, float alpha, const float* src, float* dst,
                   int64_t stride, int64_t offset) {
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, N, stride)},

@@ -345,6 +345,15 @@ hipError_t launch_cost_l2(int64_t n, const float* pred, const float* truth, floa
                           float* error, hipStream_t s);
 hipError_t launch_xent_logistic(int64_t n, const float* pred, const float* truth, float* delta,
                                 float* error, hipStream_t s);
+// lstm.hip: the gate stage of one LSTM time step (w / u / dw / du in the
+// order f, i, g, o; a du entry may be null; c_state and dc are in / out)
+hipError_t launch_lstm_gates_forward(int64_t n, const float* const w[4], const float* const u[4],
+                                     float* c_state, float* h_state, float* cell_slice,
+                                     float* out_slice, hipStream_t s);
+hipError_t launch_lstm_gates_backward(int64_t n, const float* const w[4], const float* const u[4],
+                                      const float* cell_i, const float* cprev,
+                                      const float* delta_i, float* dc, float* const dw[4],
+                                      float* const du[4], hipStream_t s);
 // TNNCuda addvv/subvv/mulvv/fmavv (op 0..3), fmavss, inverseSqrt
 hipError_t launch_vv(int op, int64_t n, const float* a, int64_t inca, const float* b, int64_t incb,
                      const float* c, int64_t incc, float* d, int64_t incd, hipStream_t s);

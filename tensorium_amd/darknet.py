@@ -15,7 +15,9 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292), and the
   classifier kinds connected / dropout / softmax / cost / logistic
   (parseConnected 146-152, parseDropOut 301-331, parseLogistic 714-720,
-  parseSoftmax 722-738, parseCost 740-755).
+  parseSoftmax 722-738, parseCost 740-755), and lstm (TLSTMLayer,
+  nlstmlayer.pas; parseLSTM 501-504) with ``[net]``'s ``time_steps`` and
+  ``inputs`` (nparser.pas:813-818, 962-972).
 * ``load_weights`` / ``write_weights``: the darknet .weights layout read by
   TDarknetParser.loadWeights (nparser.pas:1275-1330): int32 major, minor,
   revision, then ``seen`` as uint64 when major*10+minor >= 2 (else uint32),
@@ -23,7 +25,9 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   rolling_variance)[n] when batch-normalized, weights[n*c*k*k]
   (loadConvolutionalWeights, nparser.pas:1140-1185); per connected layer
   biases[O], weights[O*I], then (scales, rolling_mean, rolling_variance)[O]
-  when batch-normalized (loadConnectedWeights, nparser.pas:1102-1128).
+  when batch-normalized (loadConnectedWeights, nparser.pas:1102-1128); per
+  lstm layer eight connected blocks in the order wf wi wg wo uf ui ug uo
+  (nparser.pas:1347-1357).
 * ``fuse_batchnorm``: TBaseConvolutionalLayer.fuseBatchNorm
   (nConvolutionLayer.pas:102-126) in float32: p = scale / sqrt(max(var,
   1e-6)); bias -= mean * p; W *= p.
@@ -79,7 +83,7 @@ class Layer:
     index: int
     kind: str            # convolutional | shortcut | route | upsample | yolo |
                          # maxpool | local_avgpool | connected | dropout |
-                         # softmax | cost | logistic
+                         # softmax | cost | logistic | lstm
     c: int               # input channels / height / width
     h: int
     w: int
@@ -102,6 +106,8 @@ class Layer:
     groups: int = 1            # softmax
     temperature: float = 1.0
     noloss: bool = False
+    steps: int = 1             # lstm: time steps; its batch is Network.batch div steps
+    gate: str = ""             # a connected block of an lstm layer: wf .. uo
 
     def __post_init__(self):
         self.stride_x = self.stride_x or self.stride
@@ -131,6 +137,8 @@ def _flag(sec: Section, key: str) -> bool:
 
 # kinds that read params.c / h / w, which the reference leaves stale after a
 # layer that is no TBaseImageLayer (nparser.pas:913-919)
+LSTM_GATES = ("wf", "wi", "wg", "wo", "uf", "ui", "ug", "uo")  # file / update order
+
 _IMAGE_KINDS = ("convolutional", "conv", "shortcut", "route", "concat", "upsample", "yolo",
                 "maxpool", "max", "local_avgpool")
 
@@ -140,17 +148,29 @@ class Network:
 
     def __init__(self, sections: list[Section], batch: int | None = None):
         net = sections[0]
-        self.batch = batch if batch is not None else net.int("batch", 1)
+        # Neural.batch := mini_batch * timeSteps (nparser.pas:962-972); a
+        # batch argument replaces the whole product (ABatch, 802-803)
+        self.time_steps = net.int("time_steps", 1)
+        if self.time_steps < 1:
+            raise ValueError(f"[net] time_steps={self.time_steps}")
+        self.batch = batch if batch is not None else net.int("batch", 1) * self.time_steps
         self.h, self.w, self.c = net.int("height"), net.int("width"), net.int("channels", 3)
         self.layers: list[Layer] = []
         c, h, w = self.c, self.h, self.w
         flat = False  # a [connected] has been planned: c, h, w are the parser's no longer
+        self.inputs = c * h * w
+        if self.inputs == 0:  # no image shape: rows of inputs= floats (nparser.pas:813-818)
+            self.inputs = net.int("inputs", 0)
+            if self.inputs < 1:
+                raise ValueError("[net] has neither an image shape nor inputs=")
+            self.h = self.w = self.c = 0
+            c, h, w, flat = self.inputs, 1, 1, True
         for sec in sections[1:]:
             i = len(self.layers)
             if flat and sec.kind in _IMAGE_KINDS:
-                raise ValueError(f"[{sec.kind}] layer {i} after a [connected] layer: the reference "
-                                 "plans it on the image shape of an earlier layer "
-                                 "(nparser.pas:913-919); refused")
+                raise ValueError(f"[{sec.kind}] layer {i} after a [connected] or [lstm] layer, or "
+                                 "in a network of inputs= rows: the reference plans it on the "
+                                 "image shape of an earlier layer (nparser.pas:913-919); refused")
             if sec.kind in ("convolutional", "conv"):
                 size = sec.int("size", 1)
                 stride = sec.int("stride", 1)
@@ -210,6 +230,19 @@ class Network:
                             activation=_act(sec.get("activation", "relu")),
                             bn=_flag(sec, "batch_normalize"))
                 flat = True
+            elif sec.kind == "lstm":
+                # parseLSTM (nparser.pas:501-504); the layer's own batch is
+                # Network.batch div time_steps (nlstmlayer.pas:44) — the
+                # reference truncates, here the remainder is refused
+                o = sec.int("output", 1)
+                if o < 1 or c * h * w < 1:
+                    raise ValueError(f"[lstm] layer {i}: {c * h * w} inputs, output={o}")
+                if self.batch % self.time_steps:
+                    raise ValueError(f"[lstm] layer {i}: batch {self.batch} is no multiple of "
+                                     f"time_steps {self.time_steps}")
+                lay = Layer(i, "lstm", c, h, w, o, 1, 1, filters=o, bn=_flag(sec, "batch_normalize"),
+                            steps=self.time_steps)
+                flat = True
             elif sec.kind == "dropout":
                 # probability is a single; scale := 1 / (1.0 - probability) in
                 # double, stored as single (ndropoutlayer.pas:65)
@@ -249,9 +282,24 @@ class Network:
         return [l for l in self.layers if l.kind == "convolutional"]
 
     def param_layers(self) -> list[Layer]:
-        """The layers that own parameters, in file order (loadWeights'
-        order, nparser.pas:1309-1325)."""
-        return [l for l in self.layers if l.kind in ("convolutional", "connected")]
+        """The parameter blocks in file order (loadWeights' order,
+        nparser.pas:1309-1357): the convolutional and connected layers, and
+        for an lstm layer its eight connected sub-layers wf wi wg wo ([O][O])
+        uf ui ug uo ([O][inputs]) as connected blocks carrying the layer's
+        index and their name in ``gate``."""
+        out = []
+        for l in self.layers:
+            if l.kind in ("convolutional", "connected"):
+                out.append(l)
+            elif l.kind == "lstm":
+                for g in LSTM_GATES:
+                    n = l.filters if g[0] == "w" else l.in_size
+                    out.append(Layer(l.index, "connected", n, 1, 1, l.filters, 1, 1,
+                                     filters=l.filters, bn=l.bn, gate=g))
+        return out
+
+    def lstms(self) -> list[Layer]:
+        return [l for l in self.layers if l.kind == "lstm"]
 
 
 def yolov3_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
@@ -388,6 +436,22 @@ def lenet_mnist_cfg(batch: int = 1) -> str:
     return _classifier_cfg(batch, 28, 1, body)
 
 
+def lstm_cfg(batch: int = 1, time_steps: int = 1, inputs: int = 256, hidden: int = 1024,
+             layers: int = 3, bn: bool = True, cost: bool = False) -> str:
+    """The public char-LSTM structure: ``layers`` stacked [lstm] of ``hidden``
+    outputs over rows of ``inputs`` floats, a linear [connected] back to
+    ``inputs``, [softmax], optionally [cost].  The reference's sample loads
+    its cfg from outside its tree (lstm_shakespeare_train.pas:25, 207), so
+    this is the common structure, not a file that can be compared against."""
+    out = [f"[net]\nbatch={batch}\nsubdivisions=1\ninputs={inputs}\ntime_steps={time_steps}\n"]
+    for _ in range(layers):
+        out.append(f"[lstm]\n{'batch_normalize=1' + chr(10) if bn else ''}output={hidden}\n")
+    out += [f"[connected]\noutput={inputs}\nactivation=linear\n", "[softmax]\n"]
+    if cost:
+        out.append("[cost]\ntype=sse\n")
+    return "\n".join(out)
+
+
 # ---- parameters -------------------------------------------------------------
 
 @dataclass
@@ -499,7 +563,278 @@ def fuse_batchnorm(l: Layer, p: ConvParams) -> ConvParams:
     return ConvParams(b, w)
 
 
-class HipDarknet:
+class _LstmLayers:
+    """The lstm layers of a driver (TLSTMLayer.forwardGPU / backwardGPU /
+    updateGPU, nlstmlayer.pas:876-1294), shared by HipDarknet and
+    HipDarknetTrain.  Rows are [step][stream]; n = streams * outputs floats
+    make one step's slice.
+
+    State per layer, as the reference keeps it: ``c``, ``h``, ``dc``,
+    ``prevCell``, ``prevState`` (n floats each; never cleared by a pass),
+    ``cell`` and the layer's output (steps * n), and per sub-layer what
+    ``_fc_forward`` / ``_fc_backward`` keep for a connected layer, its output
+    and delta steps * n long.  The four w* (and the four u*) sub-layers'
+    weights, weight_updates, outputs and deltas are slices of one buffer
+    each, in the order f, i, g, o, so a strided-batched GEMM can cover them.
+
+    ``lstm_fused=False`` is the reference's call sequence, call for call
+    through the existing TNNHip methods.  ``lstm_fused=True`` is the product
+    path: one ``lstmGatesForward`` / ``lstmGatesBackward`` per step, and
+    GEMMs batched only where every output element keeps its operands and its
+    order of additions (the LSTM section)."""
+
+    W, U = LSTM_GATES[:4], LSTM_GATES[4:]
+
+    def _lstm_init(self, blocks, training):
+        torch, dev = self.torch, "cuda"
+        z = lambda n: torch.zeros(n, device=dev)  # noqa: E731
+        self.lstm = {}
+        by_layer = {}
+        for l, p in blocks:
+            by_layer.setdefault(l.index, {})[l.gate] = p
+        for l in self.net.lstms():
+            T = l.steps
+            S = self.net.batch // T
+            O, I = l.filters, l.in_size
+            n = S * O
+            ps = by_layer[l.index]
+            L = {"S": S, "T": T, "n": n, "sub": {}, "cell": z(T * n)}
+            for k in ("c", "h", "dc", "prevCell", "prevState"):
+                L[k] = z(n)
+            if not self.lstm_fused:
+                for k in ("f", "i", "g", "o", "temp", "temp2", "temp3"):
+                    L["_" + k] = z(n)
+            for side, names, K in (("w", self.W, O), ("u", self.U, I)):
+                L[side + "_w"] = z(4 * O * K)
+                L[side + "_out"] = z(4 * T * n)
+                if training:
+                    L[side + "_wu"] = z(4 * O * K)
+                    L[side + "_delta"] = z(4 * T * n)
+                for q, g in enumerate(names):
+                    p = ps[g]
+                    st = {"I": K, "w": L[side + "_w"][q * O * K:(q + 1) * O * K],
+                          "b": self._t(p.biases), "out": L[side + "_out"][q * T * n:(q + 1) * T * n]}
+                    st["w"].copy_(self._t(p.weights).reshape(-1))
+                    if l.bn:
+                        st.update(scales=self._t(p.scales), rm=self._t(p.rolling_mean),
+                                  rv=self._t(p.rolling_var))
+                    if training:
+                        st.update(wu=L[side + "_wu"][q * O * K:(q + 1) * O * K], bu=z(O),
+                                  delta=L[side + "_delta"][q * T * n:(q + 1) * T * n])
+                        if l.bn:
+                            st.update(mean=z(O), var=z(O), x=z(T * n), xn=z(T * n), su=z(O),
+                                      md=z(O), vd=z(O))
+                    L["sub"][g] = st
+            self.lstm[l.index] = L
+
+    def _t(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to("cuda")
+
+    def reset_state(self):
+        """Zero c, h, dc, prevCell and prevState of every lstm layer (no pass
+        does: the reference carries them from call to call)."""
+        for L in self.lstm.values():
+            for k in ("c", "h", "dc", "prevCell", "prevState"):
+                L[k].zero_()
+
+    # -- one sub-layer, one step: TConnectedLayer.forwardGPU / backwardGPU ----
+    def _sub_bn_forward(self, l, L, st, step, training):
+        """What follows the product (nconnectedlayer.pas:654-733) on step's
+        slice; one mean / variance pair per sub-layer, overwritten each step."""
+        hip, S, O, n = self.hip, L["S"], l.filters, L["n"]
+        out, off = st["out"], step * n
+        if not l.bn:
+            hip.forwardBias(n, out, off, O, st["b"], 1, S)
+        else:
+            if training:
+                mom = np.float32(0.05)  # bnMomentum (nconnectedlayer.pas:67)
+                keep = float(np.float32(1) - mom)
+                hip.means(n, O, S, out, off, st["mean"])
+                hip.variances(n, O, S, out, off, st["mean"], st["var"])
+                hip.scale(O, keep, st["rm"], 1)
+                hip.axpy(O, float(mom), st["mean"], 0, 1, st["rm"], 0, 1)
+                hip.scale(O, keep, st["rv"], 1)
+                hip.axpy(O, float(mom), st["var"], 0, 1, st["rv"], 0, 1)
+                hip.copy(n, out, off, 1, st["x"], off, 1)
+                hip.normalize(O, n, S, st["mean"], 1, st["var"], 1, out, off)
+                hip.copy(n, out, off, 1, st["xn"], off, 1)
+            else:
+                hip.normalize(O, n, S, st["rm"], 1, st["rv"], 1, out, off)
+            hip.forwardScaleAdd(n, out, off, O, st["scales"], st["b"], 1, S)
+        hip.ActivateArray(n, out, off, ACT["LINEAR"])
+
+    def _sub_forward(self, l, L, st, step, inp, in_step, training):
+        S, O, I, n = L["S"], l.filters, st["I"], L["n"]
+        self.hip.gemm(False, True, S, O, I, 1.0, inp, in_step * S * I, I, st["w"], 0, I, 0.0,
+                      st["out"], step * n, O)
+        self._sub_bn_forward(l, L, st, step, training)
+
+    def _sub_bn_backward(self, l, L, st, step, clamp):
+        """Up to the two products (nconnectedlayer.pas:771-821).  clamp=False:
+        lstmGatesBackward stored the slice clamped already."""
+        hip, S, T, O, n = self.hip, L["S"], L["T"], l.filters, L["n"]
+        d, off = st["delta"], step * n
+        if clamp:
+            hip.clamp(T * n, 1.0, d, d)
+            hip.DeriveArray(n, st["out"], off, ACT["LINEAR"], d)
+        hip.backwardBias(O, st["bu"], n, d, off, 1, S)
+        if l.bn:
+            hip.addDots(n, O, S, st["xn"], d, off, st["su"])
+            hip.forwardScale(n, d, off, O, st["scales"], 1, S)
+            hip.meansAndVarsDelta(n, O, S, d, st["x"], off, st["mean"], st["var"], st["md"],
+                                  st["vd"])
+            hip.normalizeDelta(n, O, S, d, st["x"], off, st["mean"], st["var"], st["md"], st["vd"])
+
+    def _sub_backward(self, l, L, st, step, inp, in_step, sd, sd_step):
+        hip, S, O, I, n = self.hip, L["S"], l.filters, st["I"], L["n"]
+        self._sub_bn_backward(l, L, st, step, True)
+        d, off = st["delta"], step * n
+        hip.gemm(True, False, O, I, S, 1.0, d, off, O, inp, in_step * S * I, I, 1.0, st["wu"], 0, I)
+        if sd is not None:
+            hip.gemm(False, False, S, I, O, 1.0, d, off, O, st["w"], 0, I, 1.0, sd,
+                     sd_step * S * I, I)
+
+    @staticmethod
+    def _at(t, off):  # a raw device pointer off floats into t
+        return t.data_ptr() + 4 * off
+
+    # -- forward ---------------------------------------------------------------
+    def _lstm_forward(self, l, inp, training):
+        hip, L = self.hip, self.lstm[l.index]
+        S, T, n, O, I = L["S"], L["T"], L["n"], l.filters, l.in_size
+        sub, out, cell = L["sub"], self.out[l.index], L["cell"]
+        inp = inp.reshape(-1)
+        if training:  # nlstmlayer.pas:901-911 (the layer's own delta: the caller)
+            for g in LSTM_GATES:
+                hip.fill(T * n, sub[g]["delta"], 0, 0.0, 1)
+        if not self.lstm_fused:
+            for i in range(T):
+                off = i * n
+                for g in self.W:
+                    self._sub_forward(l, L, sub[g], i, L["h"], 0, training)
+                for g in self.U:
+                    self._sub_forward(l, L, sub[g], i, inp, i, training)
+                for g, dst in zip("figo", ("_f", "_i", "_g", "_o")):
+                    hip.addvv(n, sub["w" + g]["out"], off, 1, sub["u" + g]["out"], off, 1, L[dst],
+                              0, 1)
+                hip.ActivateArray(n, L["_f"], 0, ACT["LOGISTIC"])
+                hip.ActivateArray(n, L["_i"], 0, ACT["LOGISTIC"])
+                hip.ActivateArray(n, L["_o"], 0, ACT["LOGISTIC"])
+                hip.ActivateArray(n, L["_g"], 0, ACT["TANH"])
+                hip.mulvv(n, L["_i"], 0, 1, L["_g"], 0, 1, L["_temp"], 0, 1)
+                hip.fmavv(n, L["c"], 0, 1, L["_f"], 0, 1, L["_temp"], 0, 1, L["c"], 0, 1)
+                hip.copy(n, L["c"], 0, 1, L["h"], 0, 1)
+                hip.ActivateArray(n, L["h"], 0, ACT["TANH"])
+                hip.mulvv(n, L["_o"], 0, 1, L["h"], 0, 1, L["h"], 0, 1)
+                hip.copy(n, L["c"], 0, 1, cell, off, 1)
+                hip.copy(n, L["h"], 0, 1, out, off, 1)
+            return
+        # the input-side products of every step and gate at once: an NT
+        # product's element is one sdot of an input row and a weight row
+        hip.gemmStridedBatched(False, True, T * S, O, I, 1.0, inp, 0, I, 0, L["u_w"], 0, I, O * I,
+                               0.0, L["u_out"], 0, O, T * n, 4)
+        for g in self.U:
+            if l.bn:  # statistics are per step
+                for i in range(T):
+                    self._sub_bn_forward(l, L, sub[g], i, training)
+            else:     # a row's bias add does not depend on its step
+                hip.forwardBias(T * n, sub[g]["out"], 0, O, sub[g]["b"], 1, T * S)
+        at = self._at
+        for i in range(T):
+            off = i * n
+            hip.gemmStridedBatched(False, True, S, O, O, 1.0, L["h"], 0, O, 0, L["w_w"], 0, O,
+                                   O * O, 0.0, L["w_out"], off, O, T * n, 4)
+            for g in self.W:
+                self._sub_bn_forward(l, L, sub[g], i, training)
+            hip.lstmGatesForward(n, [at(sub[g]["out"], off) for g in self.W],
+                                 [at(sub[g]["out"], off) for g in self.U], L["c"], L["h"],
+                                 at(cell, off), at(out, off))
+
+    # -- backward ----------------------------------------------------------------
+    def _lstm_backward(self, l, inp, sd):
+        hip, L = self.hip, self.lstm[l.index]
+        S, T, n, O, I = L["S"], L["T"], L["n"], l.filters, l.in_size
+        sub, out, cell, delta = L["sub"], self.out[l.index], L["cell"], self.delta[l.index]
+        inp = inp.reshape(-1)
+        if not self.lstm_fused:
+            for i in range(T - 1, -1, -1):
+                off = i * n
+                if i:
+                    hip.copy(n, cell, off - n, 1, L["prevCell"], 0, 1)
+                hip.copy(n, cell, off, 1, L["c"], 0, 1)
+                if i:
+                    hip.copy(n, out, off - n, 1, L["prevState"], 0, 1)
+                hip.copy(n, out, off, 1, L["h"], 0, 1)
+                for g, dst in zip("figo", ("_f", "_i", "_g", "_o")):
+                    hip.addvv(n, sub["w" + g]["out"], off, 1, sub["u" + g]["out"], off, 1, L[dst],
+                              0, 1)
+                hip.ActivateArray(n, L["_f"], 0, ACT["LOGISTIC"])
+                hip.ActivateArray(n, L["_i"], 0, ACT["LOGISTIC"])
+                hip.ActivateArray(n, L["_o"], 0, ACT["LOGISTIC"])
+                hip.ActivateArray(n, L["_g"], 0, ACT["TANH"])
+                t1, t2, t3 = L["_temp"], L["_temp2"], L["_temp3"]
+                hip.copy(n, delta, off, 1, t3, 0, 1)
+                hip.copy(n, L["c"], 0, 1, t1, 0, 1)
+                hip.ActivateArray(n, t1, 0, ACT["TANH"])
+                hip.mulvv(n, t3, 0, 1, L["_o"], 0, 1, t2, 0, 1)
+                hip.DeriveArray(n, t1, 0, ACT["TANH"], t2)
+                hip.addvv(n, L["dc"], 0, 1, t2, 0, 1, t2, 0, 1)
+                hip.copy(n, L["c"], 0, 1, t1, 0, 1)
+                hip.ActivateArray(n, t1, 0, ACT["TANH"])
+                hip.mulvv(n, t3, 0, 1, t1, 0, 1, t1, 0, 1)
+                hip.DeriveArray(n, L["_o"], 0, ACT["LOGISTIC"], t1)
+                dh = delta if i else None
+                for g, other, act in (("o", None, None), ("g", "_i", "TANH"),
+                                      ("i", "_g", "LOGISTIC"), ("f", "prevCell", "LOGISTIC")):
+                    if other is not None:
+                        hip.mulvv(n, t2, 0, 1, L[other], 0, 1, t1, 0, 1)
+                        hip.DeriveArray(n, L["_" + g], 0, ACT[act], t1)
+                    hip.copy(n, t1, 0, 1, sub["w" + g]["delta"], off, 1)
+                    self._sub_backward(l, L, sub["w" + g], i, L["prevState"], 0, dh, i - 1)
+                    hip.copy(n, t1, 0, 1, sub["u" + g]["delta"], off, 1)
+                    self._sub_backward(l, L, sub["u" + g], i, inp, i, sd, i)
+                hip.mulvv(n, t2, 0, 1, L["_f"], 0, 1, t1, 0, 1)
+                hip.copy(n, t1, 0, 1, L["dc"], 0, 1)
+            return
+        at = self._at
+        for i in range(T - 1, -1, -1):
+            off = i * n
+            if i == 0 and T > 1:  # the copies of step 1; step 0 makes none (stale operands)
+                hip.copy(n, cell, 0, 1, L["prevCell"], 0, 1)
+                hip.copy(n, out, 0, 1, L["prevState"], 0, 1)
+            cprev = at(cell, off - n) if i else L["prevCell"]
+            hprev, hoff = (out, off - n) if i else (L["prevState"], 0)
+            hip.lstmGatesBackward(n, [at(sub[g]["out"], off) for g in self.W],
+                                  [at(sub[g]["out"], off) for g in self.U], at(cell, off), cprev,
+                                  at(delta, off), L["dc"],
+                                  [at(sub[g]["delta"], off) for g in self.W],
+                                  [at(sub[g]["delta"], off) for g in self.U])
+            for g in LSTM_GATES:
+                self._sub_bn_backward(l, L, sub[g], i, False)
+            # the dW products: four outputs each, one operand shared
+            hip.gemmStridedBatched(True, False, O, O, S, 1.0, L["w_delta"], off, O, T * n, hprev,
+                                   hoff, O, 0, 1.0, L["w_wu"], 0, O, O * O, 4)
+            hip.gemmStridedBatched(True, False, O, I, S, 1.0, L["u_delta"], off, O, T * n, inp,
+                                   i * S * I, I, 0, 1.0, L["u_wu"], 0, I, O * I, 4)
+            if i:  # into the layer's own delta, slice i-1, in the reference's order
+                for g in ("wo", "wg", "wi", "wf"):
+                    hip.gemm(False, False, S, O, O, 1.0, sub[g]["delta"], off, O, sub[g]["w"], 0, O,
+                             1.0, delta, off - n, O)
+        if sd is not None:  # slice i of the layer below's delta takes step i's four products
+            for g in ("uo", "ug", "ui", "uf"):
+                hip.gemm(False, False, T * S, I, O, 1.0, sub[g]["delta"], 0, O, sub[g]["w"], 0, I,
+                         1.0, sd, 0, I)
+        hip.copy(n, cell, 0, 1, L["c"], 0, 1)
+        hip.copy(n, out, 0, 1, L["h"], 0, 1)
+
+    def _lstm_update(self, l, learning_rate, momentum, decay):
+        for g in LSTM_GATES:  # TLSTMLayer.updateGPU's order (nlstmlayer.pas:1281-1288)
+            st = self.lstm[l.index]["sub"][g]
+            self.hip.sgdUpdate(st["w"], st["wu"], st["b"], st["bu"], learning_rate,
+                               self.net.batch, decay, momentum, st.get("scales"), st.get("su"))
+
+
+class HipDarknet(_LstmLayers):
     """TNNet.forward over a darknet layer plan on the HIP backend (nnet.pas:
     275-310 selects forwardGPU per layer): every layer's output stays in a
     device buffer of its own; convolutions take BN-folded parameters
@@ -508,10 +843,15 @@ class HipDarknet:
     640-733: NT gemm, normalize by the rolling statistics + forwardScaleAdd,
     or forwardBias, then ActivateArray).  A dropout layer's output is its
     input buffer and nothing runs (ndropoutlayer.pas:156-161); softmax is
-    softmaxBatch, logistic copy + ActivateArray, cost nothing (no truth)."""
+    softmaxBatch, logistic copy + ActivateArray, cost nothing (no truth).
+    An lstm layer (``_LstmLayers``) carries c and h from one forward to the
+    next until ``reset_state()``; its batch-normalized sub-layers normalize
+    by the rolling statistics."""
 
-    def __init__(self, hip, net: Network, params: list[ConvParams], torch):
+    def __init__(self, hip, net: Network, params: list[ConvParams], torch,
+                 lstm_fused: bool = True):
         self.hip, self.net, self.torch = hip, net, torch
+        self.lstm_fused = bool(lstm_fused)
         B = net.batch
         dev = "cuda"
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
@@ -520,7 +860,11 @@ class HipDarknet:
             alias = l.kind == "dropout" and l.index > 0
             self.out.append(self.out[-1] if alias else torch.empty(B * l.out_size, device=dev))
         self.conv_params, self.fc_params = {}, {}
-        for l, p in zip(net.param_layers(), params):
+        blocks = list(zip(net.param_layers(), params))
+        self._lstm_init([b for b in blocks if b[0].gate], training=False)
+        for l, p in blocks:
+            if l.gate:
+                continue
             if l.kind == "connected":
                 st = {"w": t(p.weights), "b": t(p.biases)}
                 if l.bn:
@@ -570,6 +914,8 @@ class HipDarknet:
                 else:
                     hip.forwardBias(n, out, 0, l.filters, st["b"], 1, B)
                 hip.ActivateArray(n, out, 0, l.activation)
+            elif l.kind == "lstm":
+                self._lstm_forward(l, prev, False)
             elif l.kind == "dropout":
                 out = self.out[l.index] = prev.reshape(-1)
             elif l.kind == "softmax":
@@ -582,7 +928,7 @@ class HipDarknet:
         return self.out
 
 
-class HipDarknetTrain:
+class HipDarknetTrain(_LstmLayers):
     """One training pass of a darknet network on the HIP backend, in the
     reference's call order: TNet.forward in training (nnet.pas:275-322; each
     layer's delta zeroed by ``cuda.scale(size, 0, delta, 1)`` before its
@@ -635,13 +981,17 @@ class HipDarknetTrain:
 
     Convolutions with batch norm run ``convForwardTrain`` (training-time BN,
     nbaselayer.pas:336-370) in the forward, the heads ``convForward``.
-    ``update`` is TNNet.update (nnet.pas:371-403): ``sgdUpdate`` per layer."""
+    ``update`` is TNNet.update (nnet.pas:371-403): ``sgdUpdate`` per layer,
+    for an lstm layer on its eight sub-layers in the order wf wi wg wo uf ui
+    ug uo.  lstm layers: ``_LstmLayers``; ``lstm_fused=False`` selects the
+    reference's call sequence, call for call."""
 
     LOSS_KINDS = ("softmax", "cost", "logistic")
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
-                 seed: int = 0):
+                 seed: int = 0, lstm_fused: bool = True):
         self.hip, self.net, self.torch = hip, net, torch
+        self.lstm_fused = bool(lstm_fused)
         self.loss_scale = float(loss_scale)
         self.rng = np.random.default_rng(seed)  # default dropout seeds
         B = net.batch
@@ -666,7 +1016,11 @@ class HipDarknetTrain:
                         for l in net.layers if l.kind == "maxpool"}
         self.conv = {}
         ws = 1
-        for l, p in zip(net.param_layers(), params):
+        blocks = list(zip(net.param_layers(), params))
+        self._lstm_init([b for b in blocks if b[0].gate], training=True)
+        for l, p in blocks:
+            if l.gate:
+                continue
             n = B * l.out_size
             st = {"w": t(p.weights), "b": t(p.biases),
                   "wu": torch.zeros(p.weights.size, device=dev),
@@ -747,6 +1101,9 @@ class HipDarknetTrain:
                                    l.stride_y, l.pad, l.size, out)
             elif l.kind == "connected":
                 self._fc_forward(l, prev, out)
+            elif l.kind == "lstm":
+                hip.fill(out.numel(), self.delta[l.index], 0, 0.0, 1)
+                self._lstm_forward(l, prev, True)
             elif l.kind == "softmax":
                 n, g = B * l.in_size, l.in_size // l.groups
                 hip.softmaxBatch(g, prev, 0, B, l.in_size, l.groups, g, 1, l.temperature, out, 0)
@@ -824,6 +1181,9 @@ class HipDarknetTrain:
         convolutional and connected layer of layers 0 .. n-2 — the reference's
         loop stops before the last layer — with args.batch = net.batch."""
         for l in self.net.layers[:-1]:
+            if l.kind == "lstm":
+                self._lstm_update(l, learning_rate, momentum, decay)
+                continue
             st = self.conv.get(l.index) or self.fc.get(l.index)
             if st is None:
                 continue
@@ -881,6 +1241,8 @@ class HipDarknetTrain:
                                     l.stride_y, l.pad, l.size)
             elif l.kind == "connected":
                 self._fc_backward(l, inp.reshape(-1), sd)
+            elif l.kind == "lstm":
+                self._lstm_backward(l, inp, sd)
             elif l.kind == "dropout" and sd is not None:
                 hip.backwardDropout(sd.numel(), sd, l.probability, l.scale, self.rnd[i], sd)
             elif l.kind in ("softmax", "logistic") and sd is not None:

@@ -557,6 +557,27 @@ class TNNHip:
         check(self.lib.tns_hip_cross_entropy_logistic(self.ctx, N, _ptr(pred), _ptr(truth),
                                                       _ptr(delta), _ptr(error)))
 
+    # -- the gate stage of one LSTM time step (backend-specific, fused) -----------
+    def lstmGatesForward(self, N, w, u, c_state, h_state, cell_slice, out_slice):
+        """What TLSTMLayer.forwardGPU issues between the eight sub-layer
+        forwards and the next step (nlstmlayer.pas:933-973) as one launch.
+        w, u: the step's slices of wf wi wg wo / uf ui ug uo's outputs (four
+        buffers each, in that order); c_state in / out."""
+        check(self.lib.tns_hip_lstm_gates_forward(
+            self.ctx, N, *map(_ptr, w), *map(_ptr, u), _ptr(c_state), _ptr(h_state),
+            _ptr(cell_slice), _ptr(out_slice)))
+
+    def lstmGatesBackward(self, N, w, u, cell_i, cprev, delta_i, dc, dw, du=None):
+        """The elementwise calls of one step of TLSTMLayer.backwardGPU
+        (nlstmlayer.pas:1046-1255) as one launch: the four gate deltas,
+        clamped to [-1, 1], into the w-side slices dw and, where given, the
+        u-side slices du (f, i, g, o order; entries may be None); dc in /
+        out."""
+        du = (None,) * 4 if du is None else du
+        check(self.lib.tns_hip_lstm_gates_backward(
+            self.ctx, N, *map(_ptr, w), *map(_ptr, u), _ptr(cell_i), _ptr(cprev), _ptr(delta_i),
+            _ptr(dc), *map(_ptr, dw), *map(_ptr, du)))
+
     def sum(self, N, src, offset, out):
         check(self.lib.tns_hip_sum(self.ctx, N, _ptr(src), offset, _ptr(out)))
 
