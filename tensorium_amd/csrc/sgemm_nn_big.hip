@@ -325,26 +325,33 @@ hipError_t launch(const GemmArgs& a, hipStream_t s) {
 // registers at the 512 cap — not instantiated)
 // (form 5 is the ping-pong schedule of the 256x256 tile, sgemm_nn_pp.hip;
 // form 6 the tile at one wave per SIMD with both operands by LDS-DMA and
-// interleaved columns, sgemm_nn_w4.hip; form 7, the ping-pong tile with B
-// register-staged into k-permuted slots, is compiled into the diagnostics
-// build only: measured, not picked)
+// interleaved columns, sgemm_nn_w4.hip, its first and last two k-tiles run
+// row by row where K >= 128; form 7 the same kernel on the flat schedule
+// for every K; form 8, the ping-pong tile with B register-staged into
+// k-permuted slots, is compiled into the diagnostics build only: measured,
+// not picked)
 #ifdef TNS_DIAG_KERNELS
-int sgemm_nn_big_count() { return 8; }
+int sgemm_nn_big_count() { return 9; }
 #else
-int sgemm_nn_big_count() { return 7; }
+int sgemm_nn_big_count() { return 8; }
 #endif
 const char* sgemm_nn_big_name(int v) {
   static const char* names[] = {"256x256x32_w2x4_nn_big", "128x128x32_w2x2_nn_big",
                                 "256x128x32_w2x2_nn_big", "256x256x32_w4x4_nn_big",
                                 "256x128x16_w2x2_b2_nn_big", "256x256x32_w2x4_pp_nn_big",
-                                "256x256x32_w2x2_dma_nn_big", "256x256x32_w2x4_ppbq_nn_big"};
+                                "256x256x32_w2x2_dma_nn_big", "256x256x32_w2x2_dma_flat_nn_big",
+                                "256x256x32_w2x4_ppbq_nn_big"};
   return v >= 0 && v < sgemm_nn_big_count() ? names[v] : "";
 }
 
 // heuristic: the 256x256 tile when it gives about a block per CU, at one
 // wave per SIMD with LDS-DMA operands where it applies (form 6; 4096^3 0.983
 // -> 0.950 ms against the ping-pong form 5, which itself took 0.994 -> 0.972
-// from form 0; all bit-identical)
+// from form 0; all bit-identical).  Form 6 runs its row-ordered schedule
+// wherever K >= 128 and the flat one (form 7) below: rows measured faster
+// than flat by more than flat's round-to-round spread at every K (128 ..
+// 4096) and beta mode tried (4096^3 0.9545 -> 0.9393 ms, 1024 x 1024^3 16.37
+// -> 16.09; profiles/sgemm_w4_rows_ab.json), so no shape picks form 7
 int sgemm_nn_big_pick(const GemmArgs& a) {
   if (applies<G256>(a) && (a.M / 256) * (a.N / 256) * a.batch >= 192)
     return sgemm_nn_w4_applies(a) ? 6 : sgemm_nn_pp_applies(a) ? 5 : 0;
@@ -359,9 +366,10 @@ hipError_t launch_sgemm_nn_big(int v, const GemmArgs& a, hipStream_t s) {
     case 3: return launch<G256w16>(a, s);
     case 4: return launch<G256x128k16>(a, s);
     case 5: return launch_sgemm_nn_pp(a, s);
-    case 6: return launch_sgemm_nn_w4(a, s);
+    case 6: return launch_sgemm_nn_w4(a, s, true);
+    case 7: return launch_sgemm_nn_w4(a, s, false);
 #ifdef TNS_DIAG_KERNELS
-    case 7: return launch_sgemm_nn_pp(a, s, true);  // k-permuted B slots
+    case 8: return launch_sgemm_nn_pp(a, s, true);  // k-permuted B slots
 #endif
     default: return hipErrorInvalidValue;
   }

@@ -93,9 +93,11 @@ bool sgemm_nn_pp_applies(const GemmArgs& a);
 hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s, bool bperm = false);
 // the same tile with one wave per SIMD (4 waves of 128 x 128), A and B by
 // LDS-DMA into swizzled row images, interleaved columns (b128 B reads,
-// 16-byte C traffic) — sgemm_nn_w4.hip, nn_big form 6
+// 16-byte C traffic) — sgemm_nn_w4.hip, nn_big forms 6 (rows: the first and
+// last two k-tiles run one accumulator row at a time where K >= 128, so the
+// C loads and stores go under MFMAs) and 7 (the flat schedule throughout)
 bool sgemm_nn_w4_applies(const GemmArgs& a);
-hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s);
+hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows = true);
 // gemm(NoTrans, Trans) in the reference's sdot_avx2 order (sgemm_sdot.hip);
 // plain epilogue only
 hipError_t launch_sgemm_nt_sdot(const GemmArgs& a, hipStream_t s);
