@@ -327,20 +327,22 @@ hipError_t launch(const GemmArgs& a, hipStream_t s) {
 // form 6 the tile at one wave per SIMD with both operands by LDS-DMA and
 // interleaved columns, sgemm_nn_w4.hip, its first and last two k-tiles run
 // row by row where K >= 128; form 7 the same kernel on the flat schedule
-// for every K; form 8, the ping-pong tile with B register-staged into
-// k-permuted slots, is compiled into the diagnostics build only: measured,
-// not picked)
+// for every K, both with the flat loop's fragment addresses held in
+// registers; form 8 the rows schedule with the per-step address arithmetic
+// the kernel had before, kept for A/B (the flat one below K = 128); form 9,
+// the ping-pong tile with B register-staged into k-permuted slots, is
+// compiled into the diagnostics build only: measured, not picked)
 #ifdef TNS_DIAG_KERNELS
-int sgemm_nn_big_count() { return 9; }
+int sgemm_nn_big_count() { return 10; }
 #else
-int sgemm_nn_big_count() { return 8; }
+int sgemm_nn_big_count() { return 9; }
 #endif
 const char* sgemm_nn_big_name(int v) {
   static const char* names[] = {"256x256x32_w2x4_nn_big", "128x128x32_w2x2_nn_big",
                                 "256x128x32_w2x2_nn_big", "256x256x32_w4x4_nn_big",
                                 "256x128x16_w2x2_b2_nn_big", "256x256x32_w2x4_pp_nn_big",
                                 "256x256x32_w2x2_dma_nn_big", "256x256x32_w2x2_dma_flat_nn_big",
-                                "256x256x32_w2x4_ppbq_nn_big"};
+                                "256x256x32_w2x2_dma_b32_nn_big", "256x256x32_w2x4_ppbq_nn_big"};
   return v >= 0 && v < sgemm_nn_big_count() ? names[v] : "";
 }
 
@@ -351,7 +353,11 @@ const char* sgemm_nn_big_name(int v) {
 // wherever K >= 128 and the flat one (form 7) below: rows measured faster
 // than flat by more than flat's round-to-round spread at every K (128 ..
 // 4096) and beta mode tried (4096^3 0.9545 -> 0.9393 ms, 1024 x 1024^3 16.37
-// -> 16.09; profiles/sgemm_w4_rows_ab.json), so no shape picks form 7
+// -> 16.09; profiles/sgemm_w4_rows_ab.json), so no shape picks form 7.  From
+// K = 256 on form 6 holds its loop's fragment addresses in registers (4096^3
+// 0.9364 -> 0.9167 ms against form 8, which computes them per step; K = 128
+// measured slower that way and 160 .. 384 level, so below 256 form 6 is form
+// 8's kernel; profiles/sgemm_w4_afrag_ab.json)
 int sgemm_nn_big_pick(const GemmArgs& a) {
   if (applies<G256>(a) && (a.M / 256) * (a.N / 256) * a.batch >= 192)
     return sgemm_nn_w4_applies(a) ? 6 : sgemm_nn_pp_applies(a) ? 5 : 0;
@@ -368,8 +374,9 @@ hipError_t launch_sgemm_nn_big(int v, const GemmArgs& a, hipStream_t s) {
     case 5: return launch_sgemm_nn_pp(a, s);
     case 6: return launch_sgemm_nn_w4(a, s, true);
     case 7: return launch_sgemm_nn_w4(a, s, false);
+    case 8: return launch_sgemm_nn_w4(a, s, true, false);  // the parent's fragment addressing
 #ifdef TNS_DIAG_KERNELS
-    case 8: return launch_sgemm_nn_pp(a, s, true);  // k-permuted B slots
+    case 9: return launch_sgemm_nn_pp(a, s, true);  // k-permuted B slots
 #endif
     default: return hipErrorInvalidValue;
   }

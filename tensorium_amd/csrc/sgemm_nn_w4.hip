@@ -10,7 +10,8 @@
 //   * 4 waves (2 x 2), wave tile 128 x 128 = 4 x 4 accumulators of 32 x 32
 //     (256 accumulator registers per lane: the wave has the SIMD's whole
 //     register file to itself), so a step is 16 MFMAs = 1024 matrix-pipe
-//     cycles fed by 8 ds_read_b32 — no partner wave's staging on the SIMD;
+//     cycles fed by two ds_read2st64_b32 of A and one ds_read_b128 of B — no
+//     partner wave's staging on the SIMD;
 //   * BOTH operands stream global -> LDS by LDS-DMA (global_load_lds_dwordx4,
 //     SGPR base + one per-lane VGPR offset for the whole launch): no staging
 //     registers, no VALU transposes, no ds_write;
@@ -78,6 +79,28 @@
 // MFMA span, which the stamps do not split), 4.5 us a tile at config 4, whose
 // blocks are not in step, so part of their C traffic already ran beside
 // other CUs' loops.
+//
+// Fragment addresses (template parameter PRE).  With one wave per SIMD every
+// instruction between two MFMAs is paid for in issue time (scripts/w4_probe.hip,
+// profiles/sgemm_w4_afrag_probe.json: eight v_nop in front of a step cost what
+// eight v_mul_f32 do, 0.07 of the 0.09 ms between operands in registers and
+// the LDS reads; the same reads with no address arithmetic run within 0.01 ms
+// of the registers; 8-byte A reads with v_permlane32_swap, and the reads
+// spread over the MFMA gaps, measured slower and were not kept).  The XOR
+// swizzle and the run-time stage kept the A address out of the instruction
+// offset: 1.5 VALU a step and SALU beside them.  PRE computes the lane's 16 A
+// addresses (8 chunks x 2 k-pairs) of each stage and its B base once in front
+// of the regular loop and runs two tiles an iteration, one per stage, and an
+// odd last one: a step is its three LDS reads and one wait.  The rows
+// schedule's ends keep the per-step arithmetic.  Same values, same chains.
+// A/B against the per-step arithmetic (scripts/nn_big_ab.py --variants 8,6;
+// profiles/sgemm_w4_afrag_ab.json), medians, bit-identical everywhere:
+//   4096^3        strict beta = 0  0.9364 -> 0.9167 ms (0.979; 12.5 x the 0.0016 spread)
+//                 beta = 1         0.9337 -> 0.9167      BLAS beta = 0  0.9269 -> 0.9099
+//   1024 x 1024^3 strict beta = 0  16.06 -> 15.86 ms (0.988)
+//   4096 x 4096 x K, strict: K = 512 0.1317 -> 0.1308; 160 .. 384 level; K = 128
+//                 (no regular tile) 0.0451 -> 0.0456, slower: see PRE_MIN_TILES
+// 444 VGPRs with the 256 accumulators, no spill, code 40.5 -> 49.4 KB.
 #include <type_traits>
 
 #include "tns_internal.hpp"
@@ -88,10 +111,16 @@ namespace {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef int int4v __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(3))) float* lds_cptr;
+typedef const __attribute__((address_space(3))) floatx4* lds_cptr4;
 
 constexpr int BM = 256, BN = 256, BK = 32, NT = 256;
 constexpr int A_TILE = BM * BK, B_TILE = BK * BN, STAGE = A_TILE + B_TILE;  // floats
 constexpr int ROWS_MIN_TILES = 4;  // the rows schedule's two ends are two k-tiles each
+// the picked (rows) form holds its loop's fragment addresses in registers from
+// this many k-tiles on: measured slower below (K = 128, no regular tile, by
+// 0.5 us), level from 160 to 384, faster from 512
+constexpr int PRE_MIN_TILES = 8;
 
 __device__ __forceinline__ void dma16(const float* sbase, unsigned voff, unsigned lds) {
   unsigned keep;
@@ -113,7 +142,7 @@ __device__ __forceinline__ void dma16(const float* sbase, unsigned voff, unsigne
   } while (0)
 #endif
 
-template <bool ALPHA1, bool ROWS>
+template <bool ALPHA1, bool ROWS, bool PRE>
 __global__ __launch_bounds__(NT, 1) void sgemm_nn_w4_kernel(GemmArgs p) {
   __shared__ __attribute__((aligned(16))) float smem[2 * STAGE];
 #ifdef TNS_W4_STAMPS
@@ -251,35 +280,95 @@ __global__ __launch_bounds__(NT, 1) void sgemm_nn_w4_kernel(GemmArgs p) {
     const floatx4 v = *reinterpret_cast<const floatx4*>(st + b_col[0] + 2 * s * BN);
     b[0] = v[0]; b[1] = v[1]; b[2] = v[2]; b[3] = v[3];
   };
+  // PRE: the flat loop's fragment addresses held in registers, so that a step
+  // issues its three LDS reads (two ds_read2st64_b32 of A, the b128 of B) and
+  // no address arithmetic: per stage P the lane's A address of every k-chunk
+  // j and k-pair o (the XOR swizzle and the + 2 floats are no instruction
+  // offsets) and its B base.  Set up by pre_init() in front of the loop, whose
+  // tiles then name their stage at compile time.
+  lds_cptr ap[2][16], bp[2];
+  auto pre_init = [&]() {
+    // (computed from values made opaque here, so that none of the 34 is
+    // hoisted above the front, where the C staging sets are live)
+    int al = a_lane, sw = swz, bc = b_col[0];
+    asm volatile("" : "+v"(al), "+v"(sw), "+v"(bc));
+#pragma unroll
+    for (int P = 0; P < 2; ++P) {
+      const lds_cptr st = (lds_cptr)smem + P * STAGE;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) {
+        ap[P][c] = st + al + 4 * ((c >> 1) ^ sw) + 2 * (c & 1);
+        asm volatile("" : "+v"(ap[P][c]));
+      }
+      bp[P] = st + bc;
+      asm volatile("" : "+v"(bp[P]));
+    }
+  };
+  auto pfrag = [&](int P, int s, float (&a)[4], float (&b)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = ap[P][s][32 * BK * i];
+    const floatx4 v = *reinterpret_cast<lds_cptr4>(bp[P] + 2 * s * BN);
+    b[0] = v[0]; b[1] = v[1]; b[2] = v[2]; b[3] = v[3];
+  };
   float a0[4], b0[4], a1[4], b1[4];
   // tile t on all 16 accumulators; a0/b0 hold its step 0 on entry.  The
   // barrier that publishes tile t+1 (pub) sits before step 15 of tile t, so
   // tile t+1's first fragments are read under step 15's MFMAs and the DMA of
   // tile t+2 (dma: into tile t's stage, whose reads all completed before the
   // barrier) goes out a whole tile ahead of its use
-  auto flat_tile = [&](int t, bool pub, bool dma) {
+  // (P_: the tile's stage t & 1 as a constant; used by the PRE reads only)
+  // (always_inline: called three times, it is otherwise left a function, the
+  // accumulators passed through memory)
+  auto flat_tile_p = [&](auto P_, int t, bool pub, bool dma) __attribute__((always_inline)) {
+    constexpr int P = decltype(P_)::value;
     const float* cur = smem + (t & 1) * STAGE;
     const float* nxt = smem + ((t + 1) & 1) * STAGE;
+    auto rd = [&](bool next, int s, float (&a)[4], float (&b)[4]) {
+      if constexpr (PRE)
+        pfrag(next ? 1 - P : P, s, a, b);
+      else
+        frag(next ? nxt : cur, s, a, b);
+    };
 #pragma unroll
     for (int s = 0; s < BK / 2 - 2; s += 2) {  // steps 0 .. 13
-      frag(cur, s + 1, a1, b1);
+      rd(false, s + 1, a1, b1);
       __builtin_amdgcn_sched_barrier(0);
       mma(a0, b0);
-      frag(cur, s + 2, a0, b0);
+      rd(false, s + 2, a0, b0);
       __builtin_amdgcn_sched_barrier(0);
       mma(a1, b1);
     }
-    frag(cur, BK / 2 - 1, a1, b1);  // step 15's fragments
+    rd(false, BK / 2 - 1, a1, b1);  // step 15's fragments
     __builtin_amdgcn_sched_barrier(0);
     mma(a0, b0);                     // step 14
     __builtin_amdgcn_sched_barrier(0);
     if (pub) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of tile t+1
       __syncthreads();  // every wave's; every read of tile t complete
-      frag(nxt, 0, a0, b0);
+      rd(true, 0, a0, b0);
       __builtin_amdgcn_sched_barrier(0);
     }
     mma_dma(a1, b1, (int64_t)(t + 2) * BK, t & 1, dma);  // step 15 + tile t+2's DMA
+  };
+  // tiles t0 (even) .. t1-1; ALL: every tile publishes its successor and
+  // issues the DMA of the one after (the rows schedule's loop), otherwise
+  // where the product has them.  PRE runs two tiles an iteration, one per
+  // stage, in straight line (two bodies behind a branch on t & 1 end in
+  // accumulator spills), and an odd last one
+  auto flat_loop = [&](auto ALL_, int t0, int t1) {
+    constexpr bool ALL = decltype(ALL_)::value;
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    if constexpr (PRE) {
+      int t = t0;
+      for (; t + 1 < t1; t += 2) {
+        flat_tile_p(P0{}, t, true, ALL || t + 2 < nt);
+        flat_tile_p(P1{}, t + 1, ALL || t + 2 < nt, ALL || t + 3 < nt);
+      }
+      if (t < t1) flat_tile_p(P0{}, t, ALL || t + 1 < nt, ALL || t + 2 < nt);
+    } else {
+      for (int t = t0; t < t1; ++t) flat_tile_p(P0{}, t, ALL || t + 1 < nt, ALL || t + 2 < nt);
+    }
   };
 
   if constexpr (!ROWS) {
@@ -345,10 +434,15 @@ __global__ __launch_bounds__(NT, 1) void sgemm_nn_w4_kernel(GemmArgs p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __syncthreads();
-      frag(smem, 0, a0, b0);
+      if constexpr (PRE) {
+        pre_init();
+        pfrag(0, 0, a0, b0);
+      } else {
+        frag(smem, 0, a0, b0);
+      }
     }
     TNS_W4_STAMP(1);
-    for (int t = 0; t < nt; ++t) flat_tile(t, t + 1 < nt, t + 2 < nt);
+    flat_loop(std::false_type{}, 0, nt);
     TNS_W4_STAMP(2);
 
     // ---- epilogue --------------------------------------------------------------
@@ -547,8 +641,13 @@ __global__ __launch_bounds__(NT, 1) void sgemm_nn_w4_kernel(GemmArgs p) {
     const float* const sA = smem + (nt & 1) * STAGE;        // tile nt-2
     const float* const sB = smem + ((nt + 1) & 1) * STAGE;  // tile nt-1
     if (tb < nt - 2) {
-      frag(S0, 0, a0, b0);
-      for (int t = tb; t < nt - 2; ++t) flat_tile(t, true, true);
+      if constexpr (PRE) {  // (tb is even: stage 0)
+        pre_init();
+        pfrag(0, 0, a0, b0);
+      } else {
+        frag(S0, 0, a0, b0);
+      }
+      flat_loop(std::true_type{}, tb, nt - 2);
       fa0 = a0[0];  // row 0's step 0 of tile nt-2, read under the loop's last step
 #pragma unroll
       for (int j = 0; j < 4; ++j) fb0[j] = b0[j];
@@ -614,10 +713,14 @@ bool sgemm_nn_w4_applies(const GemmArgs& a) {
 
 // rows: the row-ordered schedule of the first and last two k-tiles where K
 // has them (K >= 128), the flat schedule below that
-hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows) {
+// pre: the flat loop reads its fragments from addresses held in registers
+// (the kernel's PRE; with rows only where K >= 256, see PRE_MIN_TILES); false
+// keeps the per-step address arithmetic, for A/B
+hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows, bool pre) {
   if (!sgemm_nn_w4_applies(a)) return hipErrorInvalidValue;
   const int64_t tiles = (a.M / BM) * (a.N / BN);
   const bool alpha1 = a.alpha == 1.0f;
+  pre = pre && (!rows || a.K / BK >= PRE_MIN_TILES);
   rows = rows && a.K / BK >= ROWS_MIN_TILES;
   for (int64_t b0 = 0; b0 < a.batch; b0 += 65535) {
     GemmArgs sub = a;
@@ -630,14 +733,21 @@ hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows) {
     sub.stamps = g_w4_stamps;
 #endif
     const dim3 grid((unsigned)tiles, (unsigned)nb);
-    if (rows && alpha1)
-      hipLaunchKernelGGL((sgemm_nn_w4_kernel<true, true>), grid, dim3(NT), 0, s, sub);
+    auto go = [&](auto R_, auto P_) {
+      constexpr bool R = decltype(R_)::value, P = decltype(P_)::value;
+      if (alpha1)
+        hipLaunchKernelGGL((sgemm_nn_w4_kernel<true, R, P>), grid, dim3(NT), 0, s, sub);
+      else
+        hipLaunchKernelGGL((sgemm_nn_w4_kernel<false, R, P>), grid, dim3(NT), 0, s, sub);
+    };
+    if (rows && pre)
+      go(std::true_type{}, std::true_type{});
     else if (rows)
-      hipLaunchKernelGGL((sgemm_nn_w4_kernel<false, true>), grid, dim3(NT), 0, s, sub);
-    else if (alpha1)
-      hipLaunchKernelGGL((sgemm_nn_w4_kernel<true, false>), grid, dim3(NT), 0, s, sub);
+      go(std::true_type{}, std::false_type{});
+    else if (pre)
+      go(std::false_type{}, std::true_type{});
     else
-      hipLaunchKernelGGL((sgemm_nn_w4_kernel<false, false>), grid, dim3(NT), 0, s, sub);
+      go(std::false_type{}, std::false_type{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

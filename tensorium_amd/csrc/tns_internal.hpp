@@ -95,9 +95,11 @@ hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s, bool bperm = fal
 // LDS-DMA into swizzled row images, interleaved columns (b128 B reads,
 // 16-byte C traffic) — sgemm_nn_w4.hip, nn_big forms 6 (rows: the first and
 // last two k-tiles run one accumulator row at a time where K >= 128, so the
-// C loads and stores go under MFMAs) and 7 (the flat schedule throughout)
+// C loads and stores go under MFMAs), 7 (the flat schedule throughout) and 8
+// (rows with pre = false: the regular loop's fragment addresses computed per
+// step instead of held in registers)
 bool sgemm_nn_w4_applies(const GemmArgs& a);
-hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows = true);
+hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows = true, bool pre = true);
 // gemm(NoTrans, Trans) in the reference's sdot_avx2 order (sgemm_sdot.hip);
 // plain epilogue only
 hipError_t launch_sgemm_nt_sdot(const GemmArgs& a, hipStream_t s);
