@@ -302,12 +302,6 @@ function tns_conv_slab_count(): longint; cdecl; external libtns;
 function tns_conv1x1_count(): longint; cdecl; external libtns;
 function tns_conv1x1_name(variant: longint): PAnsiChar; cdecl; external libtns;
 function tns_conv_slab_name(variant: longint): PAnsiChar; cdecl; external libtns;
-function tns_conv_pp_variant_count(): longint; cdecl; external libtns;
-function tns_conv_pp_variant_name(variant: longint): PAnsiChar; cdecl; external libtns;
-function tns_conv_dma_variant_count(): longint; cdecl; external libtns;
-function tns_conv_dma_variant_name(variant: longint): PAnsiChar; cdecl; external libtns;
-function tns_conv_patch_variant_count(): longint; cdecl; external libtns;
-function tns_conv_patch_variant_name(variant: longint): PAnsiChar; cdecl; external libtns;
 function tns_sdot_chains_variant_count(): longint; cdecl; external libtns;
 function tns_sdot_chains_variant_name(variant: longint): PAnsiChar; cdecl; external libtns;
 function tns_sdot_rc_variant_count(): longint; cdecl; external libtns;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """YOLOv3 batch-8 conv forward per distinct layer shape: the default choice,
 the previous shape heuristic (TNS_OPT_CONV_VARIANT = 99: sgemm_kernel.hpp
-tiles on zero-padded copies) and every plane-sized conv tile (100 + v) and ping-pong tile (200 + v),
+tiles on zero-padded copies) and every plane-sized conv tile (100 + v),
 interleaved rounds in one process.  One JSON line; per-shape lines on stderr.
 
   python scripts/conv_tile_sweep.py [--rounds 3]
@@ -29,12 +29,6 @@ def main():
     hip = TNNHip(0)
     nt = hip.convTileVariants()
     names = {100 + v: hip.lib.tns_conv_tile_variant_name(v).decode() for v in range(nt)}
-    names.update({200 + v: hip.lib.tns_conv_pp_variant_name(v).decode()
-                  for v in range(hip.convPPVariants())})
-    names.update({300 + v: hip.lib.tns_conv_dma_variant_name(v).decode()
-                  for v in range(hip.convDMAVariants())})
-    names.update({400 + v: hip.lib.tns_conv_patch_variant_name(v).decode()
-                  for v in range(hip.convPatchVariants())})
     if a.only:
         names = {k: v for k, v in names.items() if str(k) in a.only.split(",")}
     forms = [-1, 99] + list(names)

@@ -117,12 +117,6 @@ PROTOTYPES: dict[str, tuple] = {
     "tns_conv1x1_count": (C.c_int, []),
     "tns_conv1x1_name": (C.c_char_p, [C.c_int32]),
     "tns_conv_slab_name": (C.c_char_p, [C.c_int32]),
-    "tns_conv_pp_variant_count": (C.c_int, []),
-    "tns_conv_pp_variant_name": (C.c_char_p, [C.c_int32]),
-    "tns_conv_dma_variant_count": (C.c_int, []),
-    "tns_conv_dma_variant_name": (C.c_char_p, [C.c_int32]),
-    "tns_conv_patch_variant_count": (C.c_int, []),
-    "tns_conv_patch_variant_name": (C.c_char_p, [C.c_int32]),
     "tns_sdot_chains_variant_name": (C.c_char_p, [C.c_int32]),
     "tns_sdot_rc_variant_name": (C.c_char_p, [C.c_int32]),
     "tns_gemm_variant_name": (C.c_char_p, [i32]),

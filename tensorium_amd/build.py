@@ -62,10 +62,8 @@ def build_hip(verbose: bool = False, force: bool = False, out: Path | None = Non
     build.mkdir(parents=True, exist_ok=True)
     headers = sorted(CSRC.glob("*.hpp")) + [ROOT / "include" / "tns.h"]
     extra = os.environ.get("TNS_EXTRA_CFLAGS", "").split()  # A/B side builds
-    if os.environ.get("TNS_DIAG") == "1":   # + the measured, not picked forms
-        extra.append("-DTNS_DIAG_KERNELS")
     # the flag set the objects were compiled with: a different set (e.g.
-    # TNS_DIAG toggled) rebuilds everything, never a mix of the two
+    # TNS_EXTRA_CFLAGS changed) rebuilds everything, never a mix of the two
     stamp = build / "flags.stamp"
     flags = " ".join([*CXXFLAGS, *extra])
     if not stamp.exists() or stamp.read_text() != flags:

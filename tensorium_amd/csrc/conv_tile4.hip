@@ -29,18 +29,6 @@
 //     tile's first fragments are read right after it, under those MFMAs, so
 //     no LDS latency is exposed at the tile boundary; the next tile's global
 //     loads are issued at the top of a tile and stored after group SG.
-//
-// Two other B staging forms, bit-identical, kept selectable (TNS_CT4D): BD
-// gathers by dword LDS-DMA straight into the slots, BW lets a lane fill whole
-// slots (four loads along k, one ds_write_b128, lanes along 64 pixels).  On
-// YOLOv3 layer 11 at a warm clock (scripts/ct4_stamps.py: 13.3 k cycles per
-// 64-deep tile, 11.26 k of them MFMA) both are slower: BD 0.127 ms (the DMA
-// issue doubles the tile-top phase), BW 0.123 ms (last group +0.86 k
-// cycles), against 0.115 ms — although a diagnostic build without the b32 B
-// stores runs 11.6 k cycles per tile (0.100 ms).  Likewise AP (A by 16-byte
-// LDS-DMA from a slot-ordered copy of the weights made per call): 0.120 ms.
-#include <algorithm>
-#include <cstring>
 #include <type_traits>
 
 #include "tns_act.hpp"
@@ -59,18 +47,6 @@ __device__ __forceinline__ void cfor(F&& f) {
   }
 }
 
-// ds_write_addtid_b32: LDS[M0 + OFF + 4 * lane] = v (M0 saved and restored)
-template <int OFF>
-__device__ __forceinline__ void st_addtid(float v, unsigned m0v) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-      "ds_write_addtid_b32 %1 offset:%3\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v), "s"(m0v), "i"(OFF)
-      : "memory");
-}
-
 // one group's fragments of a wave: the A slot and JW B slots (4 steps each)
 template <int JW>
 struct Frag4 {
@@ -79,7 +55,6 @@ struct Frag4 {
 
 template <int BM_, int BN_, int WM_, int WN_, int BK_, int SG_, int IL_ = 0, bool SI_ = false,
           int RI_ = 0, bool ST_ = false, int JA_ = 0, int NA_ = 0, bool TA_ = false,
-          bool BD_ = false, bool BW_ = false, bool AP_ = false, bool AT_ = false,
           bool DX_ = false, bool PF_ = false>
 struct Geo4 {
   // PF: the register-staged operands of tile t+2 are loaded at the top of
@@ -96,27 +71,6 @@ struct Geo4 {
   // reference's TN GEMM + col2im sums, no col matrix (F % BK == 0: a k-tile
   // never straddles taps)
   static constexpr bool DX = DX_;
-  // AT: B stored by ds_write_addtid_b32 (address M0 + offset + 4 * lane: no
-  // address VGPR, 2 cycles a store against 4 for ds_write_b32): the gather
-  // lanes are (pixel = lane >> 2, slot component = lane & 3), so a wave's 64
-  // stores of one (slot row, fragment) are 64 consecutive dwords; the two
-  // stages' B images sit below the A images (M0 + offset reach them)
-  static constexpr bool AT = AT_;
-  // AP: A read from a pre-permuted copy of the weights (conv_tile4_permute:
-  // slot row R = 4g + q of the whole K, then m, then the slot's 4 values), so
-  // a tile's slot row is contiguous and arrives by 16-byte LDS-DMA
-  // (global_load_lds_dwordx4, 64 slots per wave-instruction): no A staging
-  // registers and no transposing stores
-  static constexpr bool AP = AP_;
-  // BW: a B gather lane fills whole 16-byte slots (its pixel's four k of one
-  // slot row: four dword loads, one ds_write_b128); lanes along 64
-  // consecutive pixels, the slot row wave-uniform (scalar k walk)
-  static constexpr bool BW = BW_;
-  // BD: B gathered straight into its LDS slots by dword LDS-DMA
-  // (buffer_load_dword ... lds; lanes = 16 pixels x the 4 slot components, so
-  // one wave-instruction fills 16 slots of a slot row): no staging registers,
-  // no ds_write, no wait on the gather before the mid-tile stores
-  static constexpr bool BD = BD_;
   // TA: A stored k-major ([K][M], gemm(Trans, ...)): a thread fills whole
   // 16-byte slots (four dword loads down k, one ds_write_b128); used for the
   // conv backward's col = W^T . delta as a 1x1 "convolution" over delta
@@ -148,15 +102,8 @@ struct Geo4 {
   static constexpr int ROWS = BK / 4;           // slot rows per image (4g + q)
   static constexpr int A_TILE = ROWS * BM * 4;  // floats
   static constexpr int STAGE = ROWS * (BM + BN) * 4;
-  static constexpr int B_TILE = ROWS * BN * 4;  // floats
   static constexpr int AU = BM * BK / 4 / NT;   // float4 A units per thread
   static constexpr int KI = BK / 4 / NW;        // B k-slots per thread
-  // ATA: with AT, the A stores too by ds_write_addtid_b32 where both stages'
-  // A images lie within M0 + offset reach (lanes = 16 rows x the 4 slot
-  // components of one k group: each of a float4's values goes to one slot row
-  // as 64 consecutive dwords)
-  static constexpr bool ATA = AT && (2 * B_TILE + 2 * A_TILE) * 4 <= 126976 &&
-                              NG * (BM / 16) % NW == 0 && NG * (BM / 16) / NW == AU;
   static_assert(BM == 16 * WM, "one 16-row strip per wave");
   static_assert(BM % 16 == 0 && BN % 16 == 0, "b128 slot rows: 64-dword multiples");
   static_assert(BK % 16 == 0 && SG <= NG - 2, "stores precede the barrier");
@@ -165,19 +112,11 @@ struct Geo4 {
   static_assert(AU >= 1 && BM * BK / 4 % NT == 0 && KI >= 1 && BK / 4 % NW == 0, "geometry");
   static_assert(NA * JA + (WN - NA) * JB == J && NA >= 1 && NA <= WN, "wave column split");
   static_assert(2 * STAGE * 4 + 64 <= 163840, "LDS");
-  static_assert(!BD || (!IL && !ST && !TA), "DMA gather: tile-top issue only");
-  static_assert(!(BD && BW), "one gather form");
-  static_assert(!AT || (!BD && !BW && !TA && !AP && !SI && 2 * B_TILE * 4 <= 98304),
-                "addtid B stores: register-staged gather, block-placed stores, B images below 96 KB");
-  static_assert(!AP || (!IL && !ST && !TA && BM % 64 == 0 && ROWS * BM % (64 * NW) == 0),
-                "A DMA: tile-top issue, whole 64-slot pieces");
-  static_assert(!DX || (TA && !AT && !BD && !BW && !AP), "DX: k-major weights, b32 gather");
-  static_assert(!PF || (!AT && !AP && !BD && !BW && !ST), "PF: register staging");
-  static constexpr int ADM = AP ? ROWS * BM / 64 / NW : 0;  // A DMA instructions per wave
-  static constexpr int AST = AP ? 0 : 4 * AU;                // A LDS stores per thread
-  static constexpr int CH = (BN + 63) / 64;  // (BW) 64-pixel chunks of a slot row
-  static constexpr int BLD = BW ? KI * CH * 4 : KI * J;            // B loads per thread
-  static constexpr int BST = BW ? KI * CH : (BD ? 0 : KI * J);      // B LDS stores per thread
+  static_assert(!DX || TA, "DX: k-major weights");
+  static_assert(!PF || !ST, "PF: register staging, no staggered halves");
+  static constexpr int AST = 4 * AU;  // A LDS stores per thread
+  static constexpr int BLD = KI * J;  // B loads per thread
+  static constexpr int BST = KI * J;  // B LDS stores per thread
 };
 
 template <class G, int KS>
@@ -188,13 +127,9 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
 #ifdef TNS_CT4_STAMPS
   const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
 #endif
-  // stage st: A image and B image (AT: [B0][B1][A0][A1], else [A0 B0][A1 B1])
-  auto a_st = [&](int st) -> float* {
-    return G::AT ? smem + 2 * G::B_TILE + st * A_TILE : smem + st * STAGE;
-  };
-  auto b_st = [&](int st) -> float* {
-    return G::AT ? smem + st * G::B_TILE : smem + st * STAGE + A_TILE;
-  };
+  // stage st: A image and B image ([A0 B0][A1 B1])
+  auto a_st = [&](int st) -> float* { return smem + st * STAGE; };
+  auto b_st = [&](int st) -> float* { return smem + st * STAGE + A_TILE; };
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w % G::WM, wn = w / G::WM;
   const int half = __builtin_amdgcn_readfirstlane(w >= G::NW / 2 ? 1 : 0);  // (ST)
@@ -234,12 +169,7 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
   };
 
   // ---- per-column state: window origin and the 9-bit tap validity mask ----
-  // gather lanes: pixel gp of a 16-column fragment, slot component gq
-  // (BD: the DMA writes lane L to float 4 * (L >> 2) + (L & 3) of its row)
-  // (BW: lane = pixel of a 64-pixel chunk)
-  // (AT: the same lane split, for consecutive-dword stores)
-  const int gp = (G::BD || G::AT) ? lane >> 2 : r16, gq = (G::BD || G::AT) ? lane & 3 : q;
-  constexpr int NCOL = G::BW ? G::CH : J;
+  // gather lanes: pixel r16 of a 16-column fragment, slot component q
   // output column n (clamped below N): its window's base offset and tap mask
   auto col_geo = [&](int n, unsigned& vb, unsigned& m) {
     n = n < N ? n : N - 1;  // past N: any valid pixel, never stored
@@ -256,22 +186,21 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
                         ((unsigned)(ic0 + kc * dil) < (unsigned)W))
              << (kr * KS + kc);
   };
-  unsigned vbase[NCOL], tmask[NCOL];
+  unsigned vbase[J], tmask[J];
+  // (the sum grouped as n0 + (16 j + r16) on purpose: grouped the other way
+  // the DX PF forms' prologue compiles to different instructions)
 #pragma unroll
-  for (int j = 0; j < NCOL; ++j) col_geo(n0 + (G::BW ? 64 * j + lane : 16 * j + gp), vbase[j], tmask[j]);
+  for (int j = 0; j < J; ++j) col_geo(n0 + (16 * j + r16), vbase[j], tmask[j]);
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.B), 0, p.conv_bytes, 0x00020000);
 
   // ---- B k-slots: slot sl = wm*KI + ii = 4g + r takes k = 16g + 4q + r (the
   // lane quarter is the slot component), advanced by BK per tile -------------
-  // (BW: entry 4 ii + i = component i of slot row w*KI + ii, wave-uniform)
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  constexpr int NKS = G::BW ? 4 * KI : KI;
-  int kc_[NKS], kr_[NKS], cc_[NKS];
+  int kc_[KI], kr_[KI], cc_[KI];
 #pragma unroll
-  for (int ii = 0; ii < NKS; ++ii) {
-    const int sl = G::BW ? wu * KI + ii / 4 : w * KI + ii;
-    const int k = 16 * (sl >> 2) + 4 * (G::BW ? ii % 4 : gq) + (sl & 3);
+  for (int ii = 0; ii < KI; ++ii) {
+    const int sl = w * KI + ii;
+    const int k = 16 * (sl >> 2) + 4 * q + (sl & 3);
     if constexpr (G::DX) {  // (k < BK <= F: tap 0, filter k)
       cc_[ii] = k;
       kr_[ii] = kc_[ii] = 0;
@@ -298,7 +227,7 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
       return;
     }
 #pragma unroll
-    for (int ii = 0; ii < NKS; ++ii) {
+    for (int ii = 0; ii < KI; ++ii) {
       if constexpr (KS == 1) {
         cc_[ii] += BK;
       } else {
@@ -314,28 +243,9 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
   };
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
-  float rbs[G::PF ? 2 : 1][KI][J];  // (unused with BD / BW; PF: one set a tile parity)
-  floatx4 rw[G::BW ? KI : 1][G::BW ? G::CH : 1];  // (BW)
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
-  auto gather_b = [&](const float* bs, auto SET) {
+  float rbs[G::PF ? 2 : 1][KI][J];  // (PF: one set a tile parity)
+  auto gather_b = [&](auto SET) {
     auto& rb = rbs[decltype(SET)::value];
-    if constexpr (G::BW) {
-#pragma unroll
-      for (int ii = 0; ii < KI; ++ii)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int e = 4 * ii + i;
-          const unsigned x = 4u * (unsigned)(cc_[e] * HW + kr_[e] * dil * W + kc_[e] * dil);
-          const int tap = kr_[e] * KS + kc_[e];
-#pragma unroll
-          for (int c = 0; c < G::CH; ++c) {
-            const bool ok = __builtin_amdgcn_ubfe(tmask[c], tap, 1) != 0;
-            const unsigned off = ok ? vbase[c] + x : 0x80000000u;
-            rw[ii][c][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
-          }
-        }
-      return;
-    }
 #pragma unroll
     for (int ii = 0; ii < KI; ++ii) {
       int y = kr_[ii] * dil, z = kc_[ii] * dil, tap = kr_[ii] * KS + kc_[ii], cc = cc_[ii];
@@ -354,29 +264,13 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
       const unsigned x = 4u * (unsigned)(cc * HW + y * W + z);
 #pragma unroll
       for (int j = 0; j < J; ++j) {
-        if constexpr (G::BD) {
-          const bool ok = __builtin_amdgcn_ubfe(tmask[j], tap, 1) != 0;
-          const unsigned off = ok ? vbase[j] + x : 0x80000000u;
-          const unsigned row = lds0 + 4u * (unsigned)((bs - smem) + ((wu * KI + ii) * BN + 16 * j) * 4);
-          unsigned keep;
-          // (a copy: an asm operand alone does not make the generic lambda
-          // capture rsrc)
-          const __amdgpu_buffer_rsrc_t rs = rsrc;
-          asm volatile(
-              "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-              "buffer_load_dword %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-              : "=&s"(keep)
-              : "v"(off), "s"(rs), "s"(row)
-              : "memory");
-        } else {
 #if defined(TNS_CT4_DIAG) && (TNS_CT4_DIAG & 1)
-          rb[ii][j] = (float)(x + j);  // diagnostic build: no B loads (timing only)
+        rb[ii][j] = (float)(x + j);  // diagnostic build: no B loads (timing only)
 #else
-          const bool ok = __builtin_amdgcn_ubfe(tmask[j], tap, 1) != 0;
-          const unsigned off = ok ? vbase[j] + x : 0x80000000u;
-          rb[ii][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+        const bool ok = __builtin_amdgcn_ubfe(tmask[j], tap, 1) != 0;
+        const unsigned off = ok ? vbase[j] + x : 0x80000000u;
+        rb[ii][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
 #endif
-        }
       }
     }
   };
@@ -389,35 +283,10 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
 #if defined(TNS_CT4_DIAG) && (TNS_CT4_DIAG & 2)
     return;  // diagnostic build: no B stores (timing only)
 #endif
-    if constexpr (G::BW) {
 #pragma unroll
-      for (int ii = 0; ii < KI; ++ii)
+    for (int ii = 0; ii < KI; ++ii)
 #pragma unroll
-        for (int c = 0; c < G::CH; ++c)
-          if (64 * (c + 1) <= BN || 64 * c + lane < BN)
-            *reinterpret_cast<floatx4*>(bs + ((wu * KI + ii) * BN + 64 * c + lane) * 4) = rw[ii][c];
-    } else if constexpr (G::AT) {
-#pragma unroll
-      for (int ii = 0; ii < KI; ++ii) {
-        // slot row w*KI + ii: fragment j's 64 dwords at row start + 256 j bytes
-        const unsigned base = lds0 + 4u * (unsigned)((bs - smem) + (wu * KI + ii) * BN * 4);
-        if (base < 65536u - 256u * J)
-          cfor<0, J>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            st_addtid<256 * j>(rb[ii][j], base);
-          });
-        else
-          cfor<0, J>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            st_addtid<32768 + 256 * j>(rb[ii][j], base - 32768u);
-          });
-      }
-    } else if constexpr (!G::BD) {  // (BD: landed by the DMA)
-#pragma unroll
-      for (int ii = 0; ii < KI; ++ii)
-#pragma unroll
-        for (int j = 0; j < J; ++j) bs[b_dst[ii] + 64 * j] = rb[ii][j];
-    }
+      for (int j = 0; j < J; ++j) bs[b_dst[ii] + 64 * j] = rb[ii][j];
   };
 
   // ---- A staging (weights [M][K]): unit = k-quad kq4 of row m; its four
@@ -433,12 +302,6 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
       const int m = idx % BM, row = idx / BM;
       a_src[u] = p.A + (int64_t)(16 * (row >> 2) + (row & 3)) * p.lda + m0 + m;
       a_dst[u] = (row * BM + m) * 4;
-    } else if constexpr (G::ATA) {
-      // unit u of wave w: group g and 16-row block mb, lane = (row, component i)
-      const int pair = u * G::NW + w, g = pair / (BM / 16), mb = 16 * (pair % (BM / 16));
-      const int m = mb + (lane >> 2), i = lane & 3;
-      a_src[u] = p.A + (m0 + m) * p.lda + 16 * g + 4 * i;
-      a_dst[u] = ((4 * g) * BM + mb) * 4;  // slot row 4g + c: + c * BM * 4 (in floats)
     } else {
       // 8 k-quads of one row per 8 lanes (128 contiguous bytes per row)
       const int lo = idx & 7, rest = idx >> 3;
@@ -447,27 +310,9 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
       a_dst[u] = (4 * (kq4 >> 2)) * BM * 4 + m * 4 + (kq4 & 3);
     }
   }
-  float4 ras[G::PF ? 2 : 1][AU];  // (unused with AP)
-  auto load_a = [&](int k0, float* as, auto SET) {
+  float4 ras[G::PF ? 2 : 1][AU];
+  auto load_a = [&](int k0, auto SET) {
     auto& ra = ras[decltype(SET)::value];
-    if constexpr (G::AP) {
-#pragma unroll
-      for (int u = 0; u < G::ADM; ++u) {
-        const int idx = wu * G::ADM + u, R = idx / (BM / 64), c = idx % (BM / 64);
-        const float* src = p.A + ((int64_t)(k0 / 4 + R) * p.M + m0 + 64 * c + lane) * 4;
-        const unsigned dst = lds0 + 4u * (unsigned)((as - smem) + (R * BM + 64 * c) * 4);
-        unsigned keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(src), "s"(dst)
-            : "memory");
-      }
-      return;
-    } else {
-      (void)as;
-    }
 #if defined(TNS_CT4_DIAG) && (TNS_CT4_DIAG & 4)
     for (int u = 0; u < AU; ++u) ra[u] = make_float4(k0, k0 + 1, k0 + 2, k0 + 3);
     return;  // diagnostic build: no A loads (timing only)
@@ -484,7 +329,6 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
   };
   auto store_a = [&](float* as, auto SET) {
     auto& ra = ras[decltype(SET)::value];
-    if constexpr (G::AP) return;  // (landed by the DMA)
 #if defined(TNS_CT4_DIAG) && (TNS_CT4_DIAG & 8)
     return;  // diagnostic build: no A stores (timing only)
 #endif
@@ -492,17 +336,6 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
     for (int u = 0; u < AU; ++u) {
       if constexpr (G::TA) {
         *reinterpret_cast<float4*>(as + a_dst[u]) = ra[u];
-      } else if constexpr (G::ATA) {
-        const float v[4] = {ra[u].x, ra[u].y, ra[u].z, ra[u].w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const unsigned base =
-              lds0 + 4u * (unsigned)((as - smem) + __builtin_amdgcn_readfirstlane(a_dst[u]) + c * BM * 4);
-          if (base < 65536u)
-            st_addtid<0>(v[c], base);
-          else
-            st_addtid<32768>(v[c], base - 32768u);
-        }
       } else {
         as[a_dst[u]] = ra[u].x;
         as[a_dst[u] + BM * 4] = ra[u].y;
@@ -565,10 +398,7 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < JW; ++j)
-        if constexpr (G::AT)  // (transposed tile: rows = pixels, columns = filters)
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.b[j][i], f.a[i], acc[j], 0, 0, 0);
-        else
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[i], f.b[j][i], acc[j], 0, 0, 0);
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[i], f.b[j][i], acc[j], 0, 0, 0);
   };
 
 #ifdef TNS_CT4_STAMPS
@@ -590,19 +420,17 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
   const int nt = K / BK;
   Frag f0, f1;
   if (nt > 0) {
-    load_a(0, a_st(0), S0{});
-    gather_b(b_st(0), S0{});
+    load_a(0, S0{});
+    gather_b(S0{});
     if constexpr (G::PF) {  // (tile 1 into set 1, in flight past the barrier)
       if (nt > 1) {
         advance();
-        load_a(BK, nullptr, S1{});
-        gather_b(nullptr, S1{});
+        load_a(BK, S1{});
+        gather_b(S1{});
       }
     }
     store_a(a_st(0), S0{});
     store_b(b_st(0), S0{});
-    if constexpr (G::BD || G::AP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (G::AT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (asm stores)
     __syncthreads();
     frag(0, 0, f0);
   }
@@ -619,18 +447,13 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
       // (unconditional: past the last tile the weight rows' k is clamped
       // and the gather's offsets run past the images' range — read, unused)
       advance();
-      load_a(min((t + 2) * BK, K - BK), nullptr, SL{});
-      gather_b(nullptr, SL{});
+      load_a(min((t + 2) * BK, K - BK), SL{});
+      gather_b(SL{});
       __builtin_amdgcn_sched_barrier(0);  // keep the loads at the top of the tile
     } else if constexpr (more && !G::IL && !G::ST && !G::PF) {
       advance();
-      if constexpr (G::BD) {
-        gather_b(b_st(tx), S0{});
-        load_a((t + 1) * BK, a_st(tx), S0{});
-      } else {
-        load_a((t + 1) * BK, a_st(tx), S0{});
-        gather_b(b_st(tx), S0{});
-      }
+      load_a((t + 1) * BK, S0{});
+      gather_b(S0{});
       __builtin_amdgcn_sched_barrier(0);  // keep the loads at the top of the tile
     }
     TNS_PH(0);
@@ -643,8 +466,6 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
           // every wave's stores of tile t+1 are in; its first group is read
           // under this group's MFMAs
           TNS_PH(3);
-          if constexpr (G::BD || G::AP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if constexpr (G::AT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (asm stores)
 #ifdef TNS_CT4_STAMPS
           // every wave's arrival at tile 8's barrier (words 16 + w, realtime
           // ticks after block entry) — who the barrier waits for
@@ -659,8 +480,8 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
       if constexpr (more && G::ST)
         if (g < 2 && half == g) {
           advance();
-          load_a((t + 1) * BK, a_st(tx), S0{});
-          gather_b(b_st(tx), S0{});
+          load_a((t + 1) * BK, S0{});
+          gather_b(S0{});
           __builtin_amdgcn_sched_barrier(0);
         }
       // one scheduling region per group: the next group's fragment reads,
@@ -674,11 +495,11 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
         if (g == 0) {
           advance();
           if constexpr (G::PF) {  // (tile t+2 into this tile's set, as above)
-            load_a(min((t + 2) * BK, K - BK), nullptr, SL{});
-            gather_b(nullptr, SL{});
+            load_a(min((t + 2) * BK, K - BK), SL{});
+            gather_b(SL{});
           } else {
-            load_a((t + 1) * BK, a_st(tx), S0{});
-            gather_b(b_st(tx), S0{});
+            load_a((t + 1) * BK, S0{});
+            gather_b(S0{});
           }
         }
       }
@@ -762,40 +583,6 @@ __global__ __launch_bounds__(G::NT) void conv_tile4_kernel(GemmArgs p, int dil) 
   // ---- epilogue: forwardBias + activate, conv output [img][filter][pixel] --
   const bool fuse = p.epi == EPI_BIAS_ACT;
   const int act = p.act;
-  if constexpr (G::AT) {
-    // the MFMAs ran with the operands swapped (same products, same k order:
-    // bit-identical): lane (r16, q) holds filter m0 + wm*16 + r16 at the four
-    // consecutive pixels 16j + 4q + e, one 16-byte store where they are in
-    // one image (every image's pixel count a multiple of 4)
-    const int64_t row = m0 + wm * 16 + r16;
-    const float bi = fuse ? p.bias[row] : 0.0f;
-    const bool v4 = (p.conv_ohw & 3) == 0 && (p.strideC & 3) == 0 && (p.ldc & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
-#pragma unroll
-    for (int j = 0; j < JW; ++j) {
-      const int nb = n0 + coff * 16 + 16 * j + 4 * q;
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fuse ? act_apply_cheap(acc[j][e] + bi, act) : acc[j][e];
-      if (v4) {
-        if (nb < N) {
-          const int img = nb / p.conv_ohw, pix = nb - img * p.conv_ohw;
-          *reinterpret_cast<float4*>(p.C + (int64_t)img * p.strideC + pix + row * p.ldc) =
-              make_float4(v[0], v[1], v[2], v[3]);
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int n = nb + e;
-          if (n < N) {
-            const int img = n / p.conv_ohw, pix = n - img * p.conv_ohw;
-            p.C[(int64_t)img * p.strideC + pix + row * p.ldc] = v[e];
-          }
-        }
-      }
-    }
-    return;
-  }
   if constexpr (G::DX) {
     const int64_t row0 = m0 + wm * 16 + 4 * q;
 #pragma unroll
@@ -882,38 +669,16 @@ struct TileInfo4 {
   {BMv, BNv, BKv, launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv>>, \
    "conv_tile4<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv ",ri" #RIv    \
    ",j" #JAv "x" #NAv ">"}
-#define TNS_CT4D(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, BDv, BWv)                          \
-  {BMv, BNv, BKv,                                                                            \
-   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, 0, 0, false, BDv, BWv>>, \
-   "conv_tile4<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv ",ri" #RIv    \
-   ",bd" #BDv ",bw" #BWv ">"}
-#define TNS_CT4UD(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv, BDv, BWv)                 \
-  {BMv, BNv, BKv,                                                                              \
-   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, false, BDv, BWv>>, \
-   "conv_tile4<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv ",ri" #RIv      \
-   ",j" #JAv "x" #NAv ",bd" #BDv ",bw" #BWv ">"}
-#define TNS_CT4A(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv)                                 \
-  {BMv, BNv, BKv,                                                                                \
-   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, false, false, false, \
-                  true>>,                                                                        \
-   "conv_tile4_ap<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv ",ri" #RIv      \
-   ",j" #JAv "x" #NAv ">"}
-#define TNS_CT4X(BMv, BNv, WMv, WNv, BKv, SGv, RIv, JAv, NAv)                                  \
-  {BMv, BNv, BKv,                                                                             \
-   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, false, RIv, false, JAv, NAv, false, false, \
-                  false, false, true>>,                                                       \
-   "conv_tile4_at<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",ri" #RIv ",j" #JAv   \
-   "x" #NAv ">"}
 #define TNS_CT4P(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv)                           \
   {BMv, BNv, BKv,                                                                             \
    launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, false, false,  \
-                  false, false, false, false, true>>,                                        \
+                  true>>,                                                                    \
    "conv_tile4_pf<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv ",ri" #RIv \
    ",j" #JAv "x" #NAv ">"}
 #define TNS_CT4PI(BMv, BNv, WMv, WNv, BKv, SGv, ILv, SIv, RIv, JAv, NAv)                     \
   {BMv, BNv, BKv,                                                                             \
    launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, ILv, SIv, RIv, false, JAv, NAv, false, false, \
-                  false, false, false, false, true>>,                                        \
+                  true>>,                                                                    \
    "conv_tile4_pf<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",il" #ILv ",si" #SIv  \
    ",ri" #RIv ",j" #JAv "x" #NAv ">"}
 const TileInfo4 kTiles4[] = {
@@ -950,44 +715,6 @@ const TileInfo4 kTiles4[] = {
     TNS_CT4P(64, 32, 4, 1, 32, 0, false, 0, 0, 0),       // 25 (13: 26^2 1x1 layers)
     TNS_CT4PI(64, 176, 4, 2, 32, 0, 2, false, 3, 6, 1),  // 26 (18 + loads interleaved: stride 2)
     TNS_CT4PI(64, 176, 4, 2, 32, 0, 0, true, 3, 6, 1),   // 27 (18 + stores interleaved: stride 1)
-#ifdef TNS_DIAG_KERNELS  // (diagnostics build only: measured, not picked)
-    // PF forms measured and not picked (sweeps: profiles/r05_conv_fwd_sweep.json):
-    // 26^2 0.1296 (PF alone) / 0.1311 (IL + SI) / 0.1273 (64-deep) against
-    // 0.1268 for 27; 13^2 0.141 / 0.143 / 0.136 against 0.134 for 21; the
-    // 64-deep 128 x 176 PF form spills, the 32-deep ones 2-3 % behind 3
-    TNS_CT4P(64, 176, 4, 2, 32, 0, false, 3, 6, 1),      // 28 (18)
-    TNS_CT4P(128, 48, 8, 1, 64, 1, true, 2, 0, 0),       // 29 (21)
-    TNS_CT4P(64, 96, 4, 1, 32, 0, false, 3, 0, 0),       // 30 (8)
-    TNS_CT4PI(64, 176, 4, 2, 32, 0, 2, true, 3, 6, 1),   // 31 (18, IL + SI)
-    TNS_CT4PI(64, 176, 4, 2, 64, 1, 2, true, 2, 6, 1),   // 32 (17, IL + SI)
-    TNS_CT4PI(128, 48, 8, 1, 64, 1, 2, true, 2, 0, 0),   // 33 (21, IL + SI)
-    TNS_CT4PI(128, 48, 8, 1, 64, 0, 2, true, 2, 0, 0),   // 34 (21, IL + SI in group 0)
-    TNS_CT4PI(128, 176, 8, 1, 32, 0, 0, false, 3, 0, 0), // 35 (0, PF)
-    TNS_CT4PI(128, 176, 8, 1, 32, 0, 0, true, 3, 0, 0),  // 36 (0, PF + SI)
-    TNS_CT4PI(128, 176, 8, 1, 32, 0, 2, false, 3, 0, 0), // 37 (0, PF + IL)
-    // B by dword LDS-DMA (BD) / slot-wise (BW): bit-exact, measured slower
-    // than the register-staged b32 stores on every class (kept selectable)
-    TNS_CT4D(128, 176, 8, 1, 64, 1, true, 2, true, false),          // 38 (3, BD)
-    TNS_CT4D(128, 176, 8, 1, 64, 1, true, 2, false, true),          // 39 (3, BW)
-    TNS_CT4UD(64, 176, 4, 2, 32, 0, false, 3, 6, 1, false, true),   // 40 (18, BW)
-    // A by 16-byte LDS-DMA from the pre-permuted weights (AP): bit-exact,
-    // slower on every class measured (52^2 0.114 -> 0.120 ms, 26^2 0.128 ->
-    // 0.138, 13^2 0.138 -> 0.155, 1x1 0.021 -> 0.023; permute pass included)
-    TNS_CT4A(128, 176, 8, 1, 64, 1, true, 2, 0, 0),                 // 41 (3)
-    // B stored by ds_write_addtid_b32 with operands swapped in the MFMA (AT:
-    // gather lanes 16 pixels x 4 k, 16-byte epilogue stores), the picked
-    // shapes: timed slower on every layer class (profiles/r04_conv_at_sweep.json:
-    // 104^2 3x3 0.123 -> 0.137 ms, 52^2 0.117 -> 0.127,
-    // 26^2 0.133 -> 0.163, 13^2 0.147 -> 0.218, 1x1 52^2 0.022 -> 0.024) —
-    // the gather's 4 k rows per load instruction touch 4x the cache lines
-    TNS_CT4X(128, 176, 8, 1, 64, 2, 0, 0, 0),    // 42 (1)
-    TNS_CT4X(128, 176, 8, 1, 64, 1, 2, 0, 0),    // 43
-    TNS_CT4X(64, 176, 4, 2, 32, 0, 3, 6, 1),     // 44 (18)
-    TNS_CT4X(128, 48, 8, 1, 64, 1, 2, 0, 0),     // 45 (21)
-    TNS_CT4X(64, 96, 4, 1, 32, 0, 3, 0, 0),      // 46 (8)
-    TNS_CT4X(64, 32, 4, 1, 32, 0, 0, 0, 0),      // 47 (13)
-    TNS_CT4X(64, 64, 4, 2, 32, 0, 0, 0, 0),      // 48 (11)
-#endif
 };
 // A k-major (TA): col = W^T . delta of the conv backward (conv_tile4_dx_*)
 #define TNS_CT4T(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv)                      \
@@ -998,7 +725,7 @@ const TileInfo4 kTiles4[] = {
 #define TNS_CT4TP(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv)                      \
   {BMv, BNv, BKv,                                                                      \
    launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, true, false, \
-                  false, false, false, false, true>>,                                   \
+                  true>>,                                                               \
    "conv_tile4_ta_pf<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv   \
    ",ri" #RIv ",j" #JAv "x" #NAv ">"}
 const TileInfo4 kTiles4T[] = {
@@ -1022,14 +749,13 @@ constexpr int kNumTiles4T = sizeof(kTiles4T) / sizeof(kTiles4T[0]);
 // k-major A, tap-major k (DX): state.delta of stride-1 3x3 layers
 #define TNS_CT4DX(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv)                          \
   {BMv, BNv, BKv,                                                                          \
-   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, true, false,  \
-                  false, false, false, true>>,                                             \
+   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, true, true>>, \
    "conv_tile4_dx<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv         \
    ",ri" #RIv ",j" #JAv "x" #NAv ">"}
 #define TNS_CT4DXP(BMv, BNv, WMv, WNv, BKv, SGv, SIv, RIv, JAv, NAv)                         \
   {BMv, BNv, BKv,                                                                          \
-   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, true, false,  \
-                  false, false, false, true, true>>,                                       \
+   launch_g4<Geo4<BMv, BNv, WMv, WNv, BKv, SGv, 0, SIv, RIv, false, JAv, NAv, true, true,   \
+                  true>>,                                                                  \
    "conv_tile4_dx_pf<" #BMv "x" #BNv "x" #BKv ",w" #WMv "x" #WNv ",g" #SGv ",si" #SIv      \
    ",ri" #RIv ",j" #JAv "x" #NAv ">"}
 const TileInfo4 kTiles4DX[] = {
@@ -1055,10 +781,6 @@ constexpr int kNumTiles4DX = sizeof(kTiles4DX) / sizeof(kTiles4DX[0]);
 #undef TNS_CT4DXP
 #undef TNS_CT4
 #undef TNS_CT4U
-#undef TNS_CT4D
-#undef TNS_CT4A
-#undef TNS_CT4UD
-#undef TNS_CT4X
 #undef TNS_CT4T
 #undef TNS_CT4TP
 #undef TNS_CT4P
@@ -1067,27 +789,7 @@ constexpr int kNumTiles4 = sizeof(kTiles4) / sizeof(kTiles4[0]);
 
 }  // namespace
 
-__global__ void permute_weights_kernel(const float* __restrict__ A, float* __restrict__ Ap, int M,
-                                       int K, int64_t n) {
-  // Ap[((R * M) + m) * 4 + i] = A[m][16 (R >> 2) + 4 i + (R & 3)]
-  for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < n;
-       o += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(o & 3);
-    const int64_t rest = o >> 2;
-    const int m = (int)(rest % M), R = (int)(rest / M);
-    Ap[o] = A[(int64_t)m * K + 16 * (R >> 2) + 4 * i + (R & 3)];
-  }
-}
-
 int conv_tile4_count() { return kNumTiles4; }
-bool conv_tile4_is_ap(int v) { return v >= 0 && v < kNumTiles4 && std::strstr(kTiles4[v].name, "_ap<"); }
-hipError_t conv_tile4_permute(const float* A, float* Ap, int64_t M, int64_t K, hipStream_t s) {
-  if (M <= 0 || K % 16 || M * K > 0x7fffffffLL) return hipErrorInvalidValue;
-  const int64_t n = M * K;
-  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(permute_weights_kernel, dim3(blocks), dim3(256), 0, s, A, Ap, (int)M, (int)K, n);
-  return hipGetLastError();
-}
 const char* conv_tile4_name(int v) { return v >= 0 && v < kNumTiles4 ? kTiles4[v].name : ""; }
 int conv_tile4_bk(int v) { return v >= 0 && v < kNumTiles4 ? kTiles4[v].bk : 0; }
 

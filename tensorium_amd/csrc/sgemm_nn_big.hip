@@ -329,20 +329,14 @@ hipError_t launch(const GemmArgs& a, hipStream_t s) {
 // row by row where K >= 128; form 7 the same kernel on the flat schedule
 // for every K, both with the flat loop's fragment addresses held in
 // registers; form 8 the rows schedule with the per-step address arithmetic
-// the kernel had before, kept for A/B (the flat one below K = 128); form 9,
-// the ping-pong tile with B register-staged into k-permuted slots, is
-// compiled into the diagnostics build only: measured, not picked)
-#ifdef TNS_DIAG_KERNELS
-int sgemm_nn_big_count() { return 10; }
-#else
+// the kernel had before, kept for A/B (the flat one below K = 128))
 int sgemm_nn_big_count() { return 9; }
-#endif
 const char* sgemm_nn_big_name(int v) {
   static const char* names[] = {"256x256x32_w2x4_nn_big", "128x128x32_w2x2_nn_big",
                                 "256x128x32_w2x2_nn_big", "256x256x32_w4x4_nn_big",
                                 "256x128x16_w2x2_b2_nn_big", "256x256x32_w2x4_pp_nn_big",
                                 "256x256x32_w2x2_dma_nn_big", "256x256x32_w2x2_dma_flat_nn_big",
-                                "256x256x32_w2x2_dma_b32_nn_big", "256x256x32_w2x4_ppbq_nn_big"};
+                                "256x256x32_w2x2_dma_b32_nn_big"};
   return v >= 0 && v < sgemm_nn_big_count() ? names[v] : "";
 }
 
@@ -375,9 +369,6 @@ hipError_t launch_sgemm_nn_big(int v, const GemmArgs& a, hipStream_t s) {
     case 6: return launch_sgemm_nn_w4(a, s, true);
     case 7: return launch_sgemm_nn_w4(a, s, false);
     case 8: return launch_sgemm_nn_w4(a, s, true, false);  // the parent's fragment addressing
-#ifdef TNS_DIAG_KERNELS
-    case 9: return launch_sgemm_nn_pp(a, s, true);  // k-permuted B slots
-#endif
     default: return hipErrorInvalidValue;
   }
 }

@@ -125,7 +125,7 @@ struct tns_ctx {
 namespace {
 
 enum { SLOT_COL = 0, SLOT_STAGE1 = 1, SLOT_STAGE2 = 2, SLOT_STAGE3 = 3, SLOT_DW = 4, SLOT_BN = 5,
-       SLOT_MLP = 6, SLOT_WT = 7, SLOT_COL_DX = 8, SLOT_WPERM = 9, SLOT_RES_A = 10,
+       SLOT_MLP = 6, SLOT_WT = 7, SLOT_COL_DX = 8, /* 9: unused */ SLOT_RES_A = 10,
        SLOT_RES_B = 11, SLOT_COUNT = 12 };
 static_assert(SLOT_COUNT == tns_ctx::kSlots, "one scratch buffer per slot");
 
@@ -1839,6 +1839,16 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
   const int64_t outImg = oh * ow, ks = kSize * kSize, k = C * ks;
   if (oh <= 0 || ow <= 0 || batch <= 0) return TNS_OK;
   const bool needs_col = ks != 1 || dilation != 1 || stride != 1;
+  // logistic / tanh: bias in the GEMM epilogue (activation 4 = linear there),
+  // the transcendental activation in its own pass
+  const bool transc = act_transcendental(activation);
+  const int epi_act = transc ? 4 : activation;
+  auto activate_tail = [&]() -> int {
+    if (!bias_act || !transc) return TNS_OK;
+    OpTimer t(c, TNS_OP_ACTIVATE);
+    return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
+                      "activate launch");
+  };
   // TNS_CONV_FUSED: implicit GEMM (batch folded into N: one launch with the
   // tile shapes of pick_conv_variant, measured at or ahead of the per-image
   // GEMM on every YOLOv3 layer, 1x1 ones included)
@@ -1857,6 +1867,31 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
     // implicit GEMM: batch folded into N, B gathered from zero-padded images
     if (!input || !weights || !out || (bias_act && !biases))
       return set_error(TNS_ERR_ARG, "conv_forward: null operand");
+    if (g_conv_variant >= 200 && g_conv_variant < 500)
+      return set_error(TNS_ERR_UNSUPPORTED,
+                       "conv variant %lld: the ping-pong, LDS-DMA-ring and input-patch tile "
+                       "families (200..499) were removed",
+                       (long long)g_conv_variant);
+    // the implicit-GEMM operands of images b0 .. b0 + nb, gathered from stored
+    // images of Hs x Ws (img floats each): mode 1 = zero-padded copies through
+    // the k-table kt, 2 = bounds-checked against a border of pad
+    auto conv_args = [&](const float* src, int64_t img, int64_t Hs, int64_t Ws, int mode,
+                         const int* kt, int64_t pad, int64_t b0, int64_t nb) {
+      GemmArgs a{};
+      a.M = filters; a.N = nb * outImg; a.K = k;
+      a.alpha = 1.0f; a.beta = 0.0f; a.beta_mode = BETA_ZERO;
+      a.A = weights; a.lda = k; a.strideA = 0;
+      a.B = src + b0 * img; a.ldb = outImg; a.strideB = img;
+      a.C = out + b0 * outImg * filters; a.ldc = outImg; a.strideC = outImg * filters;
+      a.batch = 1; a.epi = bias_act ? EPI_BIAS_ACT : EPI_NONE; a.bias = biases;
+      a.act = epi_act;
+      a.conv = mode; a.ktab = kt; a.ktab_n = kt ? (int)(k + KTAB_PAD) : 0;
+      a.conv_H = (int)Hs; a.conv_W = (int)Ws; a.conv_ow = (int)ow; a.conv_ohw = (int)outImg;
+      a.conv_sY = (int)stride; a.conv_sX = (int)stride;
+      a.conv_pH = (int)pad; a.conv_pW = (int)pad;
+      a.conv_bytes = (int)(4 * nb * img);
+      return a;
+    };
     // short-k first layers (3-channel 3x3): the direct kernel, one HBM pass
     // (TNS_OPT_CONV_VARIANT >= 0 forces a GEMM tile instead)
     if (g_conv_variant < 0 && conv_direct_applies(C, kSize, filters)) {
@@ -1878,19 +1913,12 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
         {
           OpTimer t(c, TNS_OP_GEMM);
           const hipError_t e = launch_conv1x1(cv, weights, input, bias_act ? biases : nullptr, out,
-                                              batch, filters, k, outImg,
-                                              act_transcendental(activation) ? 4 : activation,
-                                              c->stream);
+                                              batch, filters, k, outImg, epi_act, c->stream);
           if (e == hipErrorInvalidValue)
             return set_error(TNS_ERR_UNSUPPORTED, "conv1x1 form %d does not fit this layer", cv);
           if (int r = hip_status(e, "conv1x1 launch")) return r;
         }
-        if (bias_act && act_transcendental(activation)) {
-          OpTimer t(c, TNS_OP_ACTIVATE);
-          return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
-                            "activate launch");
-        }
-        return TNS_OK;
+        return activate_tail();
       }
     } else if (g_conv_variant >= 600) {
       return set_error(TNS_ERR_UNSUPPORTED, "conv1x1 forms need a 1x1 stride-1 unpadded layer");
@@ -1913,7 +1941,7 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
         sa.input = input; sa.weights = weights; sa.bias = bias_act ? biases : nullptr; sa.out = out;
         sa.batch = batch; sa.C = C; sa.H = H; sa.W = W; sa.M = filters; sa.K = k; sa.ks = kSize;
         sa.stride = stride; sa.pad = padding; sa.dil = dilation; sa.ow = ow; sa.ohw = outImg;
-        sa.act = act_transcendental(activation) ? 4 : activation;
+        sa.act = epi_act;
         {
           OpTimer t(c, TNS_OP_GEMM);
           const hipError_t e = launch_conv_slab(sv, sa, slab, c->stream);
@@ -1921,92 +1949,40 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
             return set_error(TNS_ERR_UNSUPPORTED, "conv slab form %d does not fit this layer", sv);
           if (int r = hip_status(e, "conv slab launch")) return r;
         }
-        if (bias_act && act_transcendental(activation)) {
-          OpTimer t(c, TNS_OP_ACTIVATE);
-          return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
-                            "activate launch");
-        }
-        return TNS_OK;
+        return activate_tail();
       }
     }
-    // tiles with a bounds-checked gather from the unpadded images where they
-    // apply: the LDS-DMA ring (conv_dma.hip), the ping-pong schedule
-    // (conv_pp.hip) or the plane-sized lock-step tiles (conv_tile.hip);
-    // TNS_OPT_CONV_VARIANT 400 + v forces conv_patch tile v (3x3 stride-1
-    // pad-1 layers), 300 + v conv_dma tile v, 200 + v conv_pp
-    // tile v, 100 + v conv_tile tile v, 0..99 the sgemm_kernel.hpp shapes
+    // plane-sized tiles with a bounds-checked gather from the unpadded images
+    // (conv_tile.hip) where picked, or forced by TNS_OPT_CONV_VARIANT = 100 + v
+    // (0..99: the sgemm_kernel.hpp shapes, below)
     {
-      int tv = -1, pv = -1, dv = -1, ev = -1;
+      int tv = -1;
       const int64_t img0 = C * H * W;
-      if ((kSize == 1 || kSize == 3) && k % 32 == 0 && img0 * 4 <= 0x7fffffffLL &&
-          (g_conv_variant < 0 || g_conv_variant >= 100)) {
-        GemmArgs probe{};
-        probe.M = filters; probe.N = batch * outImg; probe.K = k;
-        probe.conv_sY = (int)stride;
-        probe.A = weights; probe.lda = k;
-        const bool patch_ok = kSize == 3 && stride == 1 && padding == 1 && dilation == 1;
-        if (g_conv_variant >= 400)
-          ev = patch_ok ? (int)(g_conv_variant - 400) : -1;
-        else if (g_conv_variant >= 300)
-          dv = (int)(g_conv_variant - 300);
-        else if (g_conv_variant >= 200)
-          pv = (int)(g_conv_variant - 200);
-        else if (g_conv_variant >= 100)
+      if ((kSize == 1 || kSize == 3) && k % 32 == 0 && img0 * 4 <= 0x7fffffffLL) {
+        if (g_conv_variant >= 100) {
           tv = (int)(g_conv_variant - 100);
-        else if ((dv = conv_dma_pick(probe, (int)kSize)) < 0)
+        } else if (g_conv_variant < 0) {
+          GemmArgs probe{};
+          probe.M = filters; probe.N = batch * outImg; probe.K = k;
+          probe.conv_sY = (int)stride;
+          probe.A = weights; probe.lda = k;
           tv = conv_tile_pick(probe, (int)kSize);
-      }
-      if (pv >= 0) tv = 1000 + pv;
-      if (dv >= 0) tv = 2000 + dv;
-      if (ev >= 0) tv = 3000 + ev;
-      if (g_conv_variant >= 400 && ev < 0)
-        return set_error(TNS_ERR_UNSUPPORTED, "conv_patch needs a 3x3 stride-1 pad-1 layer");
-      if (tv >= 0) {
-        // forms reading A from the slot-ordered weights: permute them first
-        const float* wA = weights;
-        if (tv < 1000 && conv_tile_is_ap(tv)) {
-          float* wp = nullptr;
-          if (int r = ensure_scratch(c, SLOT_WPERM, filters * k, &wp)) return r;
-          OpTimer t(c, TNS_OP_GEMM);
-          if (int r = hip_status(conv_tile4_permute(weights, wp, filters, k, c->stream),
-                                 "weight permute launch"))
-            return r;
-          wA = wp;
         }
+      }
+      if (tv >= 0) {
         const int64_t chunk = std::max<int64_t>(
             1, std::min<int64_t>(0x7fffffffLL / (4 * img0),
                                  0x7fffffffLL / std::max<int64_t>(outImg, 1)));
         for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
           const int64_t nb = std::min(chunk, batch - b0);
-          GemmArgs a{};
-          a.M = filters; a.N = nb * outImg; a.K = k;
-          a.alpha = 1.0f; a.beta = 0.0f; a.beta_mode = BETA_ZERO;
-          a.A = wA; a.lda = k; a.strideA = 0;
-          a.B = input + b0 * img0; a.ldb = outImg; a.strideB = img0;
-          a.C = out + b0 * outImg * filters; a.ldc = outImg; a.strideC = outImg * filters;
-          a.batch = 1; a.epi = bias_act ? EPI_BIAS_ACT : EPI_NONE; a.bias = biases;
-          a.act = act_transcendental(activation) ? 4 : activation;
-          a.conv = 2;
-          a.conv_H = (int)H; a.conv_W = (int)W; a.conv_ow = (int)ow; a.conv_ohw = (int)outImg;
-          a.conv_sY = (int)stride; a.conv_sX = (int)stride;
-          a.conv_pH = (int)padding; a.conv_pW = (int)padding;
-          a.conv_bytes = (int)(4 * nb * img0);
+          const GemmArgs a = conv_args(input, img0, H, W, 2, nullptr, padding, b0, nb);
           OpTimer t(c, TNS_OP_GEMM);
-          hipError_t e =
-              tv >= 3000 ? launch_conv_patch(tv - 3000, a, c->stream)
-              : tv >= 2000 ? launch_conv_dma(tv - 2000, a, (int)kSize, (int)dilation, c->stream)
-              : tv >= 1000 ? launch_conv_pp(tv - 1000, a, (int)kSize, (int)dilation, c->stream)
-                           : launch_conv_tile(tv, a, (int)kSize, (int)dilation, c->stream);
+          const hipError_t e = launch_conv_tile(tv, a, (int)kSize, (int)dilation, c->stream);
           if (e == hipErrorInvalidValue)
             return set_error(TNS_ERR_UNSUPPORTED, "conv tile %d does not fit this layer", tv);
           if (int r = hip_status(e, "conv tile launch")) return r;
         }
-        if (bias_act && act_transcendental(activation)) {
-          OpTimer t(c, TNS_OP_ACTIVATE);
-          return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
-                            "activate launch");
-        }
-        return TNS_OK;
+        return activate_tail();
       }
     }
     // Materialise the zero border (padded images, no bounds checks in the
@@ -2040,19 +2016,8 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
         1, std::min<int64_t>(0x7fffffffLL / (4 * img), 0x7fffffffLL / std::max<int64_t>(outImg, 1)));
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
       const int64_t nb = std::min(chunk, batch - b0);
-      GemmArgs a{};
-      a.M = filters; a.N = nb * outImg; a.K = k;
-      a.alpha = 1.0f; a.beta = 0.0f; a.beta_mode = BETA_ZERO;
-      a.A = weights; a.lda = k; a.strideA = 0;
-      a.B = src + b0 * img; a.ldb = outImg; a.strideB = img;
-      a.C = out + b0 * outImg * filters; a.ldc = outImg; a.strideC = outImg * filters;
-      a.batch = 1; a.epi = bias_act ? EPI_BIAS_ACT : EPI_NONE; a.bias = biases;
-      a.act = act_transcendental(activation) ? 4 : activation;
-      a.conv = padded ? 1 : 2; a.ktab = kt; a.ktab_n = (int)(k + KTAB_PAD);
-      a.conv_H = (int)Hs; a.conv_W = (int)Ws; a.conv_ow = (int)ow; a.conv_ohw = (int)outImg;
-      a.conv_sY = (int)stride; a.conv_sX = (int)stride;
-      a.conv_pH = padded ? 0 : (int)padding; a.conv_pW = a.conv_pH;
-      a.conv_bytes = (int)(4 * nb * img);
+      const GemmArgs a =
+          conv_args(src, img, Hs, Ws, padded ? 1 : 2, kt, padded ? 0 : padding, b0, nb);
       OpTimer t(c, TNS_OP_GEMM);
       // (99: the sgemm_kernel.hpp shape heuristic, bypassing conv_tile)
       hipError_t e = launch_sgemm_conv_variant(g_conv_variant == 99 ? -1 : (int)g_conv_variant,
@@ -2062,12 +2027,7 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
                          (long long)g_conv_variant);
       if (int r = hip_status(e, "implicit conv launch")) return r;
     }
-    if (bias_act && act_transcendental(activation)) {
-      OpTimer t(c, TNS_OP_ACTIVATE);
-      return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
-                        "activate launch");
-    }
-    return TNS_OK;
+    return activate_tail();
   }
   const float* Bp;
   int64_t strideB;
@@ -2088,16 +2048,11 @@ int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W
     Bp = input;
   }
   // conv GEMM with forwardBias + activate fused into the epilogue
-  // (logistic / tanh: bias in the epilogue, activation in its own pass)
-  const bool transc = act_transcendental(activation);
   if (int r = do_gemm(c, false, false, filters, outImg, k, 1.0f, weights, k, 0, Bp, outImg,
                       strideB, 0.0f, out, outImg, outImg * filters, batch,
-                      bias_act ? EPI_BIAS_ACT : EPI_NONE, biases, transc ? 4 : activation, true))
+                      bias_act ? EPI_BIAS_ACT : EPI_NONE, biases, epi_act, true))
     return r;
-  if (!transc || !bias_act) return TNS_OK;
-  OpTimer t(c, TNS_OP_ACTIVATE);
-  return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
-                    "activate launch");
+  return activate_tail();
 }
 }  // namespace
 
@@ -2617,12 +2572,6 @@ int tns_conv_dx_tile_count(void) { return conv_tile4_ta_count(); }
 int tns_conv_dx_conv_count(void) { return conv_tile4_dx3_count(); }
 int tns_conv_dw_res_count(void) { return dw_res_count(); }
 int tns_conv_dw_tile_count(void) { return dw_tile_count(); }
-int tns_conv_pp_variant_count(void) { return conv_pp_count(); }
-const char* tns_conv_pp_variant_name(int32_t v) { return conv_pp_name(v); }
-int tns_conv_dma_variant_count(void) { return conv_dma_count(); }
-const char* tns_conv_dma_variant_name(int32_t v) { return conv_dma_name(v); }
-int tns_conv_patch_variant_count(void) { return conv_patch_count(); }
-const char* tns_conv_patch_variant_name(int32_t v) { return conv_patch_name(v); }
 const char* tns_conv_tile_variant_name(int32_t v) { return conv_tile_name(v); }
 const char* tns_sdot_chains_variant_name(int32_t v) { return sdot_chains_variant_name(v); }
 int tns_sdot_rc_variant_count(void) { return sdot_rc_variant_count(); }

@@ -90,7 +90,7 @@ int sgemm_nn_big_pick(const GemmArgs& a);
 hipError_t launch_sgemm_nn_big(int v, const GemmArgs& a, hipStream_t s);
 // the 256x256 NN tile on the ping-pong schedule (sgemm_nn_pp.hip; form 5)
 bool sgemm_nn_pp_applies(const GemmArgs& a);
-hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s, bool bperm = false);
+hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s);
 // the same tile with one wave per SIMD (4 waves of 128 x 128), A and B by
 // LDS-DMA into swizzled row images, interleaved columns (b128 B reads,
 // 16-byte C traffic) — sgemm_nn_w4.hip, nn_big forms 6 (rows: the first and
@@ -166,12 +166,6 @@ hipError_t launch_conv_slab(int v, const ConvSlabArgs& c, float* slab, hipStream
 // (conv_tile4.hip; K % the form's k-tile == 0): conv_tile variants
 // conv_tile_count() - conv_tile4_count() + v
 int conv_tile4_count();
-// conv_tile4 forms that read A from a pre-permuted copy of the weights
-// (conv_tile4_permute into M*K floats of scratch first); conv_tile_is_ap
-// takes a conv_tile index (conv_tile.hip)
-bool conv_tile4_is_ap(int v);
-bool conv_tile_is_ap(int v);
-hipError_t conv_tile4_permute(const float* A, float* Ap, int64_t M, int64_t K, hipStream_t s);
 const char* conv_tile4_name(int v);
 int conv_tile4_bk(int v);
 hipError_t launch_conv_tile4(int v, const GemmArgs& a, int ks, int dil, hipStream_t s);
@@ -209,24 +203,6 @@ int conv_tile4_dx3s2_pick(int64_t batch, int64_t C, int64_t H, int64_t W, int64_
 hipError_t launch_conv_tile4_dx3s2(int v, const float* wt, const float* delta, float* im,
                                    int64_t batch, int64_t C, int64_t H, int64_t W, int64_t F,
                                    int64_t pad, int64_t oh, int64_t ow, hipStream_t s);
-// implicit-GEMM convolution on the ping-pong schedule (conv_pp.hip): same
-// operands and limits as conv_tile; conv_pp_pick = -1 where not measured faster
-int conv_pp_count();
-const char* conv_pp_name(int v);
-int conv_pp_pick(const GemmArgs& a, int ks);
-hipError_t launch_conv_pp(int v, const GemmArgs& a, int ks, int dil, hipStream_t s);
-// implicit-GEMM convolution fed by an LDS-DMA ring (conv_dma.hip): same
-// operands and limits as conv_tile
-int conv_dma_count();
-const char* conv_dma_name(int v);
-int conv_dma_pick(const GemmArgs& a, int ks);
-hipError_t launch_conv_dma(int v, const GemmArgs& a, int ks, int dil, hipStream_t s);
-// 3x3 stride-1 pad-1 convolution reading B from a staged input patch
-// (conv_patch.hip): whole output rows per tile
-int conv_patch_count();
-const char* conv_patch_name(int v);
-int conv_patch_pick(const GemmArgs& a);
-hipError_t launch_conv_patch(int v, const GemmArgs& a, hipStream_t s);
 // conv backward dW in the sdot order with the im2col matrix generated in the
 // staging (dw_tile.hip): part[b][m][n] = alpha * sdot over the pixels of
 // delta_b[m][.] and the im2col row n of image b (BETA_STORE; the caller adds

@@ -457,18 +457,6 @@ class TNNHip:
         """Plane-sized implicit-conv tiles (setConvVariant(100 + v))."""
         return int(self.lib.tns_conv_tile_variant_count())
 
-    def convPPVariants(self) -> int:
-        """Ping-pong implicit-conv tiles (setConvVariant(200 + v))."""
-        return int(self.lib.tns_conv_pp_variant_count())
-
-    def convPatchVariants(self) -> int:
-        """Input-patch 3x3 stride-1 conv tiles (setConvVariant(400 + v))."""
-        return int(self.lib.tns_conv_patch_variant_count())
-
-    def convDMAVariants(self) -> int:
-        """LDS-DMA-ring implicit-conv tiles (setConvVariant(300 + v))."""
-        return int(self.lib.tns_conv_dma_variant_count())
-
     def sdotChainsVariants(self) -> int:
         return int(self.lib.tns_sdot_chains_variant_count())
 

@@ -901,7 +901,9 @@ def test_conv_tile_variants_bit_exact(hip, torch_cuda, ora):
     100 + v): bounds-checked gather from unpadded images, 1x1 and 3x3,
     strides 1/2, dilation 2, ragged N, fused bias + leaky/linear/relu and the
     separate logistic pass; tiles whose rows do not divide the filter count
-    report UNSUPPORTED."""
+    report UNSUPPORTED.  200 + v, 300 + v and 400 + v selected tile families
+    that were removed: TNS_ERR_UNSUPPORTED (status 4), and the default choice
+    works again right after."""
     from tensorium_amd._abi import TnsError
     ntiles = hip.convTileVariants()
     assert ntiles >= 4
@@ -917,105 +919,18 @@ def test_conv_tile_variants_bit_exact(hip, torch_cuda, ora):
                     continue
                 ran += 1
                 assert np.array_equal(got, ref), (v, batch, C, H, F, k, s, p, act, d)
+        batch, C, H, F, k, s, p, act, d = TILE_CASES[0]
+        for removed in (200, 300, 400):
+            hip.setConvVariant(removed)
+            with pytest.raises(TnsError, match=r"tns status 4: .*removed"):
+                conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, 3, seed=0, dil=d)
+            hip.setConvVariant(-1)
+            got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, 3, seed=0,
+                                 dil=d)
+            assert np.array_equal(got, ref), removed
     finally:
         hip.setConvVariant(-1)
     assert ran >= 2 * ntiles
-
-
-PP_CASES = TILE_CASES + [(2, 32, 9, 128, 1, 1, 0, 4, 1), (2, 64, 9, 128, 1, 1, 0, 4, 1),
-                         (2, 64, 26, 512, 3, 1, 1, 9, 1), (1, 64, 13, 1024, 3, 1, 1, 1, 1)]
-
-
-def test_conv_pp_variants_bit_exact(hip, torch_cuda, ora):
-    """Every ping-pong conv tile (conv_pp.hip, TNS_OPT_CONV_VARIANT = 200 + v):
-    two wave groups alternating compute and staging, staging loads issued a
-    phase early; one, two and many k-tiles (the prologue, the peeled last
-    tiles), 1x1 / 3x3, strides 1/2, dilation 2, ragged N, fused epilogues and
-    the separate logistic pass — bit-identical to the oracle."""
-    from tensorium_amd._abi import TnsError
-    nv = hip.convPPVariants()
-    if nv == 0:
-        pytest.skip("measured-and-not-picked family: diagnostics build only (TNS_DIAG=1)")
-    assert nv >= 3
-    ran = 0
-    try:
-        for v in range(nv):
-            hip.setConvVariant(200 + v)
-            for i, (batch, C, H, F, k, s, p, act, d) in enumerate(PP_CASES):
-                try:
-                    got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, 3,
-                                         seed=100 + i, dil=d)
-                except TnsError:
-                    continue
-                ran += 1
-                assert np.array_equal(got, ref), (v, batch, C, H, F, k, s, p, act, d)
-    finally:
-        hip.setConvVariant(-1)
-    assert ran >= 3 * nv
-
-
-def test_conv_dma_variants_bit_exact(hip, torch_cuda, ora):
-    """Every LDS-DMA-ring conv tile (conv_dma.hip, TNS_OPT_CONV_VARIANT =
-    300 + v): B gathered into LDS by dword LDS-DMA (out-of-window taps land
-    as 0 through the range check), A by 16-byte LDS-DMA into the swizzled
-    slot image, three stages two tiles ahead; one, two, three and many
-    k-tiles, 1x1 / 3x3, strides 1/2, dilation 2, ragged N, fused epilogues
-    and the separate logistic pass — bit-identical to the oracle."""
-    from tensorium_amd._abi import TnsError
-    nv = hip.convDMAVariants()
-    if nv == 0:
-        pytest.skip("measured-and-not-picked family: diagnostics build only (TNS_DIAG=1)")
-    assert nv >= 3
-    ran = 0
-    cases = PP_CASES + [(2, 96, 11, 128, 1, 1, 0, 9, 1), (3, 32, 7, 64, 3, 1, 1, 9, 1)]
-    try:
-        for v in range(nv):
-            hip.setConvVariant(300 + v)
-            for i, (batch, C, H, F, k, s, p, act, d) in enumerate(cases):
-                try:
-                    got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, 3,
-                                         seed=200 + i, dil=d)
-                except TnsError:
-                    continue
-                ran += 1
-                assert np.array_equal(got, ref), (v, batch, C, H, F, k, s, p, act, d)
-    finally:
-        hip.setConvVariant(-1)
-    assert ran >= 3 * nv
-
-
-PATCH_CASES = [(2, 32, 17, 128, 3, 1, 1, 9, 1), (2, 32, 13, 256, 3, 1, 1, 0, 1),
-               (1, 64, 26, 128, 3, 1, 1, 1, 1), (3, 32, 52, 128, 3, 1, 1, 9, 1),
-               (2, 64, 13, 1024, 3, 1, 1, 9, 1), (1, 32, 104, 128, 3, 1, 1, 4, 1),
-               (2, 32, 7, 64, 3, 1, 1, 9, 1), (1, 32, 23, 128, 3, 1, 1, 9, 1)]
-
-
-def test_conv_patch_variants_bit_exact(hip, torch_cuda, ora):
-    """Every input-patch conv tile (conv_patch.hip, TNS_OPT_CONV_VARIANT =
-    400 + v): whole output rows per tile (partial last row groups), the
-    5-channel zero-halo patch by dword LDS-DMA, tap offsets from the per-tile
-    table — bit-identical to the oracle; tiles that do not fit a plane
-    report UNSUPPORTED."""
-    from tensorium_amd._abi import TnsError
-    nv = hip.convPatchVariants()
-    if nv == 0:
-        pytest.skip("measured-and-not-picked family: diagnostics build only (TNS_DIAG=1)")
-    assert nv >= 3
-    ran = 0
-    try:
-        for v in range(nv):
-            hip.setConvVariant(400 + v)
-            for i, (batch, C, H, F, k, s, p, act, d) in enumerate(PATCH_CASES):
-                try:
-                    got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, 3,
-                                         seed=300 + i, dil=d)
-                except TnsError:
-                    continue
-                ran += 1
-                assert np.array_equal(got, ref), (v, batch, C, H, F, k, s, p, act, d)
-    finally:
-        hip.setConvVariant(-1)
-    assert ran >= 2 * nv
 
 
 SLAB_CASES = [
