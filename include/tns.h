@@ -504,7 +504,11 @@ int tns_hip_mlp_train_step(tns_ctx* ctx, int32_t nlayers, const int64_t* widths,
  * im2col is skipped for 1x1 / stride 1 / dilation 1 (ntensors.pas:8286-8312).
  * workspace: >= batch*C*kH*kW*oH*oW floats, or NULL to use ctx scratch.
  * NOTE: mirrors the reference's slot swap: xDilation is passed as dilationY
- * (ntensors.pas:8303); harmless for square dilation. */
+ * (ntensors.pas:8303); harmless for square dilation.  With xDilation !=
+ * yDilation the swapped im2col's column grid differs from the oH x oW the col
+ * buffer and the GEMM are sized for (the reference overruns its workspace
+ * there): TNS_ERR_UNSUPPORTED, the message naming both sizes, before anything
+ * is allocated or launched; out is left untouched. */
 int tns_hip_conv2d(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int64_t W,
                    const float* input, const float* weights, int64_t filters,
                    int64_t kH, int64_t kW, int64_t wPadding, int64_t hPadding,

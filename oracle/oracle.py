@@ -39,8 +39,8 @@ _PROTO = {
     "ora_upsample": (None, [i64, i64, i64, i64, f32, fp, fp]),
     "ora_yolo_forward": (None, [i64, i64, i64, i64, fp, fp]),
     "ora_gradient": (C.c_int, [fp, i64, i32, fp]),
-    "ora_conv2d": (None, [i64, i64, i64, i64, fp, fp, i64, i64, i64, i64, i64, i64, i64, i64, i64,
-                          fp, fp]),
+    "ora_conv2d": (C.c_int, [i64, i64, i64, i64, fp, fp, i64, i64, i64, i64, i64, i64, i64, i64,
+                             i64, fp, fp]),
     "ora_conv_forward": (None, [i64, i64, i64, i64, fp, fp, fp, i64, i64, i64, i64, i64, i32, fp,
                                 fp]),
     "ora_fuse_batchnorm": (None, [i64, i64, fp, fp, fp, fp, fp]),
@@ -173,13 +173,29 @@ def gradient(y: np.ndarray, act: int, delta: np.ndarray) -> np.ndarray:
     return delta
 
 
-def conv2d(x, w, filters, k, pad, stride, dil=1):
+def conv2d(x, w, filters, k=None, pad=None, stride=None, dil=1, *, kH=None, kW=None, wPad=None,
+           hPad=None, xStride=None, yStride=None, xDil=None, yDil=None):
+    """TTensor.Conv2D; k / pad / stride / dil set both axes, the eight keyword
+    arguments one axis each (Conv2D's own parameters).  Raises ValueError for
+    unequal dilations whose swapped im2col grid differs from the output's
+    (ora_conv2d refuses them: the reference overruns its workspace there)."""
     batch, C_, H, W = x.shape
-    oh, ow = out_dim(H, pad, k, dil, stride), out_dim(W, pad, k, dil, stride)
-    ws = np.zeros(max(batch * C_ * k * k * oh * ow, 1), np.float32)
-    out = np.zeros((batch, filters, oh, ow), np.float32)
-    lib().ora_conv2d(batch, C_, H, W, _p(x), _p(w), filters, k, k, pad, pad, stride, stride, dil,
-                     dil, _p(ws), _p(out))
+    kH, kW = (k if kH is None else kH), (k if kW is None else kW)
+    wPad, hPad = (pad if wPad is None else wPad), (pad if hPad is None else hPad)
+    xStride, yStride = (stride if xStride is None else xStride), \
+        (stride if yStride is None else yStride)
+    xDil, yDil = (dil if xDil is None else xDil), (dil if yDil is None else yDil)
+    wp = wPad if wPad >= 0 else xDil + kW // 2 - 1   # ntensors.pas:8266-8269
+    hp = hPad if hPad >= 0 else yDil + kH // 2 - 1
+    oh, ow = out_dim(H, hp, kH, yDil, yStride), out_dim(W, wp, kW, xDil, xStride)
+    if (out_dim(H, hp, kH, xDil, yStride), out_dim(W, wp, kW, yDil, xStride)) != (oh, ow):
+        raise ValueError(f"conv2d: xDilation {xDil}, yDilation {yDil}: the im2col grid differs "
+                         f"from the {oh}x{ow} output")
+    ws = np.zeros(max(batch * C_ * kH * kW * oh * ow, 1), np.float32)
+    out = np.zeros((batch, filters, max(oh, 0), max(ow, 0)), np.float32)
+    rc = lib().ora_conv2d(batch, C_, H, W, _p(x), _p(w), filters, kH, kW, wPad, hPad, xStride,
+                          yStride, xDil, yDil, _p(ws), _p(out))
+    assert rc == 0, rc
     return out
 
 

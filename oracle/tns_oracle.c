@@ -471,13 +471,22 @@ int ora_gradient(const float* x, int64_t N, int32_t act, float* delta) {
 /* ------------------------------------------------------------------------ */
 /* Conv2D / conv layer                                                       */
 /* ------------------------------------------------------------------------ */
-void ora_conv2d(int64_t batch, int64_t C, int64_t H, int64_t W, const float* input,
-                const float* weights, int64_t filters, int64_t kH, int64_t kW, int64_t wPadding,
-                int64_t hPadding, int64_t xStride, int64_t yStride, int64_t xDilation,
-                int64_t yDilation, float* workspace, float* out) {
+int ora_conv2d(int64_t batch, int64_t C, int64_t H, int64_t W, const float* input,
+               const float* weights, int64_t filters, int64_t kH, int64_t kW, int64_t wPadding,
+               int64_t hPadding, int64_t xStride, int64_t yStride, int64_t xDilation,
+               int64_t yDilation, float* workspace, float* out) {
+  /* negative padding => "same"-style default (ntensors.pas:8266-8269) */
+  if (wPadding < 0) wPadding = xDilation + kW / 2 - 1;
+  if (hPadding < 0) hPadding = yDilation + kH / 2 - 1;
   /* output size as nConvolutionLayer.outWidth/outHeight (92-100) */
   int64_t oh = out_dim(H, hPadding, kH, yDilation, yStride);
   int64_t ow = out_dim(W, wPadding, kW, xDilation, xStride);
+  /* the swapped dilations below give the im2col another column grid when
+   * xDilation != yDilation: the reference writes past its workspace there
+   * (or multiplies rows at the wrong pitch); refused, nothing written */
+  if (out_dim(H, hPadding, kH, xDilation, yStride) != oh ||
+      out_dim(W, wPadding, kW, yDilation, xStride) != ow)
+    return -1;
   int64_t kSize = kH * kW, outImg = oh * ow, k = C * kSize;
   int64_t strideB;
   const float* Bp;
@@ -495,6 +504,7 @@ void ora_conv2d(int64_t batch, int64_t C, int64_t H, int64_t W, const float* inp
   for (int64_t b = 0; b < batch; b++)
     ora_sgemm(101, 111, 111, filters, outImg, k, 1.0f, weights, k, Bp + b * strideB, outImg,
               0.0f, out + b * outImg * filters, outImg);
+  return 0;
 }
 
 void ora_conv_forward(int64_t batch, int64_t C, int64_t H, int64_t W, const float* input,

@@ -88,8 +88,12 @@ int     ora_activate(float* x, int64_t N, int32_t act);
 int     ora_gradient(const float* x, int64_t N, int32_t act, float* delta);
 
 /* TTensor.Conv2D (ntensors.pas:8252-8349): im2col (unless 1x1/s1/d1) then
- * per-image gemm(NN, filters, outHW, C*k^2, 1, W, .., 0, out_b, ..). */
-void    ora_conv2d(int64_t batch, int64_t C, int64_t H, int64_t W,
+ * per-image gemm(NN, filters, outHW, C*k^2, 1, W, .., 0, out_b, ..).
+ * Negative paddings select the reference's default (8266-8269).  Returns 0;
+ * -1, with nothing written, when xDilation != yDilation makes the im2col's
+ * column grid (the dilations go into swapped slots, 8303) differ from the
+ * oH x oW the workspace and the GEMM are sized for. */
+int     ora_conv2d(int64_t batch, int64_t C, int64_t H, int64_t W,
                    const float* input, const float* weights, int64_t filters,
                    int64_t kH, int64_t kW, int64_t wPadding, int64_t hPadding,
                    int64_t xStride, int64_t yStride, int64_t xDilation, int64_t yDilation,

@@ -1783,6 +1783,16 @@ int tns_hip_conv2d(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
   const int64_t oh = out_dim(H, hPadding, kH, yDilation, yStride);
   const int64_t ow = out_dim(W, wPadding, kW, xDilation, xStride);
   const int64_t outImg = oh * ow, kSize = kH * kW, k = C * kSize;
+  // with xDilation != yDilation the swapped im2col writes g.oh x g.ow columns
+  // per row while the col buffer and the GEMM are sized for oh x ow: the
+  // reference runs past its workspace there (or reads rows at the wrong
+  // pitch); refused before any scratch is taken or anything is launched
+  if (g.oh != oh || g.ow != ow)
+    return set_error(TNS_ERR_UNSUPPORTED,
+                     "conv2d: xDilation %lld, yDilation %lld give %lldx%lld im2col columns but "
+                     "the layer's output is %lldx%lld (ntensors.pas:8303)",
+                     (long long)xDilation, (long long)yDilation, (long long)g.oh,
+                     (long long)g.ow, (long long)oh, (long long)ow);
   if (oh <= 0 || ow <= 0 || batch <= 0) return TNS_OK;
   const float* Bp;
   int64_t strideB;

@@ -10,8 +10,32 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def conv_case(hip, torch, ora, batch, C, H, F, k, s, p, act, fused, seed=0, dil=1):
-    x = ora.uniform(batch * C * H * H, 3, seed, 0.0, 1.0).reshape(batch, C, H, H)
+def _odim(n, k, s, p, d=1):
+    return (n + 2 * p - (d * (k - 1) + 1)) // s + 1
+
+
+def _nonsquare(cases, geo=lambda c: (c[5], c[6], c[7], c[9] if len(c) > 9 else 1)):
+    """Check a list of (batch, C, H, W, F, k, s, p, act[, dil]) cases at import
+    time (on the CPU too): H != W, oh != ow and, at stride 2, H and W of
+    different parity (the four pixel-parity classes then have four different
+    sizes).  geo(case) -> (k, s, p, dil) for lists laid out otherwise."""
+    for c in cases:
+        H, W = c[2], c[3]
+        k, s, p, d = geo(c)
+        assert H != W, c
+        assert _odim(H, k, s, p, d) != _odim(W, k, s, p, d), c
+        assert s != 2 or H % 2 != W % 2, c
+    return cases
+
+
+def _sq(case):
+    """(batch, C, H, W, F, ...) -> ((batch, C, H, F, ...), W)."""
+    return tuple(case[:3]) + tuple(case[4:]), case[3]
+
+
+def conv_case(hip, torch, ora, batch, C, H, F, k, s, p, act, fused, seed=0, dil=1, W=None):
+    W = H if W is None else W
+    x = ora.uniform(batch * C * H * W, 3, seed, 0.0, 1.0).reshape(batch, C, H, W)
     sc = float(np.sqrt(2.0 / (k * k * C)))
     w = ora.uniform(F * C * k * k, 30 + seed, seed, -sc, sc)
     b = ora.uniform(F, 60 + seed, seed, -0.1, 0.1)
@@ -19,7 +43,7 @@ def conv_case(hip, torch, ora, batch, C, H, F, k, s, p, act, fused, seed=0, dil=
         ora.conv_forward(x, w, b, F, k, s, p, act)
     dx, dw, db = (torch.from_numpy(t).cuda() for t in (x, w, b))
     out = torch.full(ref.shape, float("nan"), device="cuda")
-    hip.convForward(batch, C, H, H, dx, dw, db, F, k, s, p, dil, act, None, out, fused=fused)
+    hip.convForward(batch, C, H, W, dx, dw, db, F, k, s, p, dil, act, None, out, fused=fused)
     hip.finish()
     return out.cpu().numpy(), ref
 
@@ -30,6 +54,22 @@ def conv_case(hip, torch, ora, batch, C, H, F, k, s, p, act, fused, seed=0, dil=
     (1, 4, 20, 33, 3, 2, 1, 1), (2, 3, 13, 6, 5, 1, 2, 0)])
 def test_conv_forward_small(hip, torch_cuda, ora, fused, batch, C, H, F, k, s, p, act):
     got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, fused)
+    assert np.array_equal(got, ref)
+
+
+# Non-square twins of the case lists below: (batch, C, H, W, F, ...).  Every
+# entry of the C ABI takes H and W separately; on square planes a swapped
+# H/W, oh/ow or py/px in a kernel's index arithmetic is invisible.
+SMALL_NS = _nonsquare([
+    (2, 3, 17, 11, 8, 3, 1, 1, 9), (3, 5, 12, 19, 7, 3, 2, 1, 9), (2, 16, 9, 14, 5, 1, 1, 0, 4),
+    (1, 4, 20, 7, 33, 3, 2, 1, 1), (2, 3, 13, 22, 6, 5, 1, 2, 0)])
+
+
+@pytest.mark.parametrize("fused", [0, 1, 2, 3])
+@pytest.mark.parametrize("case", SMALL_NS)
+def test_conv_forward_small_nonsquare(hip, torch_cuda, ora, fused, case):
+    sq, W = _sq(case)
+    got, ref = conv_case(hip, torch_cuda, ora, *sq, fused, W=W)
     assert np.array_equal(got, ref)
 
 
@@ -112,6 +152,51 @@ def test_conv_implicit_dilation(hip, torch_cuda, ora, pad):
         hip.setConvPad(-1)
 
 
+IMPLICIT_NS = _nonsquare([
+    (2, 3, 17, 23, 8, 3, 1, 1, 9), (3, 5, 12, 17, 70, 3, 2, 1, 9), (1, 7, 31, 18, 129, 3, 1, 1, 9),
+    (2, 13, 26, 15, 40, 3, 2, 1, 1), (2, 33, 19, 10, 64, 3, 1, 1, 9),
+    (1, 64, 52, 20, 128, 3, 1, 1, 9)])
+IMPLICIT_DIL_NS = _nonsquare([(2, 4, 21, 14, 12, 3, 1, 2, 9, 2)])
+
+
+@pytest.mark.parametrize("pad", [0, 1])
+@pytest.mark.parametrize("variant", [-1, 0, 1, 2, 3, 4, 5, 6, 12, 13, 14, 15, 16, 18, 19, 20, 21,
+                                     22])
+def test_conv_implicit_variants_nonsquare(hip, torch_cuda, ora, variant, pad):
+    """test_conv_implicit_variants_bit_exact on H != W planes."""
+    from tensorium_amd._abi import TnsError
+    hip.setConvVariant(variant)
+    hip.setConvPad(pad)
+    ran = 0
+    try:
+        for i, case in enumerate(IMPLICIT_NS):
+            sq, W = _sq(case)
+            try:
+                got, ref = conv_case(hip, torch_cuda, ora, *sq, fused=3, seed=i, W=W)
+            except TnsError:
+                assert variant not in CONV_VARIANTS and variant >= 0, variant
+                return
+            ran += 1
+            assert np.array_equal(got, ref), (variant, pad, case)
+    finally:
+        hip.setConvVariant(-1)
+        hip.setConvPad(-1)
+    assert ran >= 2
+
+
+@pytest.mark.parametrize("pad", [0, 1])
+def test_conv_implicit_dilation_nonsquare(hip, torch_cuda, ora, pad):
+    hip.setConvPad(pad)
+    try:
+        for i, (batch, C, H, W, F, k, s, p, act, d) in enumerate(IMPLICIT_DIL_NS):
+            for fused in (3, 2):
+                got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, fused,
+                                     seed=i, dil=d, W=W)
+                assert np.array_equal(got, ref), fused
+    finally:
+        hip.setConvPad(-1)
+
+
 # direct kernel (conv_direct.hip): 3-channel 3x3 layers with 16 or 32
 # filters — ragged pixel counts, strides, paddings beyond the window,
 # dilation, every activation form (logistic/tanh evaluated in the kernel)
@@ -126,6 +211,19 @@ def test_conv_direct_bit_exact(hip, torch_cuda, ora, fused, case):
     batch, C, H, F, k, s, p, act, dil = case
     got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, fused, seed=5,
                          dil=dil)
+    assert np.array_equal(got, ref), case
+
+
+DIRECT_NS = _nonsquare([(2, 3, 17, 30, 32, 3, 1, 1, 9, 1), (3, 3, 12, 21, 16, 3, 2, 1, 0, 1),
+                        (1, 3, 30, 13, 32, 3, 1, 2, 6, 2), (1, 3, 40, 9, 32, 3, 2, 0, 4, 1)])
+
+
+@pytest.mark.parametrize("fused", [1, 3])
+@pytest.mark.parametrize("case", DIRECT_NS)
+def test_conv_direct_nonsquare(hip, torch_cuda, ora, fused, case):
+    batch, C, H, W, F, k, s, p, act, dil = case
+    got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, fused, seed=5,
+                         dil=dil, W=W)
     assert np.array_equal(got, ref), case
 
 
@@ -166,6 +264,19 @@ def test_conv_backward_matches_oracle(hip, torch_cuda, ora, batch, C, H, F, k, s
     assert np.array_equal(dbu.cpu().numpy(), rbu)
 
 
+BACKWARD_NS = _nonsquare([
+    (2, 3, 17, 11, 8, 3, 1, 1, 9), (3, 5, 12, 19, 7, 3, 2, 1, 9), (2, 16, 9, 14, 5, 1, 1, 0, 4),
+    (1, 32, 26, 15, 64, 3, 2, 1, 9), (10, 4, 9, 6, 8, 3, 1, 1, 9)])
+
+
+@pytest.mark.parametrize("case", BACKWARD_NS)
+def test_conv_backward_matches_oracle_nonsquare(hip, torch_cuda, ora, case):
+    sq, W = _sq(case)
+    got, ref = _bwd_case(hip, torch_cuda, ora, *sq, seed=sq[0] * 1000 + sq[1] * 10 + sq[2], W=W)
+    for n, g, r in zip(("delta", "state_delta", "weight_updates", "bias_updates"), got, ref):
+        assert np.array_equal(g, r), n
+
+
 @pytest.mark.parametrize("idx", [0, 2, 11, 74])
 def test_conv_backward_yolov3_batch8(hip, torch_cuda, ora, idx):
     """YOLOv3 layer shapes at batch 8: the dW partial sums of all images in
@@ -197,23 +308,33 @@ DX_CASES = [(2, 64, 13, 64, 3, 1, 1, 9), (2, 128, 13, 64, 3, 1, 1, 1), (1, 128, 
             (2, 64, 9, 128, 1, 1, 0, 4), (3, 64, 11, 96, 3, 1, 1, 9)]
 
 
-def _dx_case(hip, torch, ora, batch, C, H, F, k, s, p, act, seed):
+def _bwd_case(hip, torch, ora, batch, C, H, F, k, s, p, act, seed, W=None, neg_zero=False):
+    """One convBackward against the oracle; returns the GPU's and the
+    oracle's (delta, state_delta, weight_updates, bias_updates)."""
+    W = H if W is None else W
     rng = np.random.default_rng(seed)
-    oh = (H + 2 * p - k) // s + 1
-    x = rng.uniform(-1, 1, (batch, C, H, H)).astype(np.float32)
+    oh, ow = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    x = rng.uniform(-1, 1, (batch, C, H, W)).astype(np.float32)
     w = rng.uniform(-0.3, 0.3, F * C * k * k).astype(np.float32)
-    out = rng.uniform(-1, 1, (batch, F, oh, oh)).astype(np.float32)
+    out = rng.uniform(-1, 1, (batch, F, oh, ow)).astype(np.float32)
     d0 = rng.uniform(-1, 1, out.shape).astype(np.float32)
     bu0 = rng.uniform(-1, 1, F).astype(np.float32)
     wu0 = rng.uniform(-1, 1, F * C * k * k).astype(np.float32)
     sd0 = rng.uniform(-1, 1, x.shape).astype(np.float32)
+    if neg_zero:
+        sd0[0, 0, 0, :2] = -0.0  # a pixel whose every skipped tap must stay skipped
     rd, rbu, rwu, rsd = d0.copy(), bu0.copy(), wu0.copy(), sd0.copy()
     ora.conv_backward(x, w, F, k, s, p, act, out, rd, rbu, rwu, rsd)
     t = lambda a: torch.from_numpy(a.copy()).cuda()  # noqa: E731
     dx, dw, dout, dd, dbu, dwu, dsd = map(t, (x, w, out, d0, bu0, wu0, sd0))
-    hip.convBackward(batch, C, H, H, dx, dw, F, k, s, p, 1, act, dout, dd, dbu, dwu, None, dsd)
+    hip.convBackward(batch, C, H, W, dx, dw, F, k, s, p, 1, act, dout, dd, dbu, dwu, None, dsd)
     hip.finish()
-    return dsd.cpu().numpy(), rsd
+    return [a.cpu().numpy() for a in (dd, dsd, dwu, dbu)], [rd, rsd, rwu, rbu]
+
+
+def _dx_case(hip, torch, ora, batch, C, H, F, k, s, p, act, seed, W=None):
+    got, ref = _bwd_case(hip, torch, ora, batch, C, H, F, k, s, p, act, seed, W=W)
+    return got[1], ref[1]
 
 
 def test_conv_backward_dx_tiles(hip, torch_cuda, ora):
@@ -299,6 +420,68 @@ def test_conv_backward_dx_conv_stride2_forms(hip, torch_cuda, ora):
     finally:
         hip.setDxConv(-1)
     assert ran >= 2 * nv
+
+
+DX_NS = _nonsquare([(2, 64, 13, 20, 64, 3, 1, 1, 9), (2, 128, 13, 9, 64, 3, 1, 1, 1),
+                    (1, 128, 20, 11, 128, 3, 2, 1, 9), (2, 64, 9, 14, 128, 1, 1, 0, 4)])
+DX3_NS = _nonsquare([(2, 64, 13, 18, 64, 3, 1, 1, 9), (3, 64, 9, 14, 128, 3, 1, 0, 9),
+                     (2, 64, 6, 11, 64, 3, 1, 2, 9), (2, 32, 15, 8, 64, 3, 1, 1, 9),
+                     # 128 channels: the forms with 128-channel tiles
+                     (2, 128, 11, 7, 128, 3, 1, 1, 1), (1, 128, 20, 13, 128, 3, 1, 1, 4)])
+# stride 2: (even, odd) and (odd, even) planes, so the pixel-parity classes
+# (0,1) and (1,0) of the transposed convolutions differ in size
+DX3S2_NS = _nonsquare([(2, 64, 14, 9, 64, 3, 2, 1, 9), (2, 32, 16, 11, 64, 3, 2, 1, 1),
+                       (1, 64, 13, 18, 128, 3, 2, 1, 9), (2, 64, 12, 7, 64, 3, 2, 0, 9),
+                       (2, 128, 10, 15, 128, 3, 2, 2, 4), (1, 128, 13, 20, 64, 3, 2, 1, 9)])
+assert {(c[2] % 2, c[3] % 2) for c in DX3S2_NS} == {(0, 1), (1, 0)}
+
+
+def _forced_dx_forms(hip, torch, ora, nv, select, cases, seed0):
+    """state.delta of every case on every forced form 0 .. nv-1 (select(v));
+    forms that report UNSUPPORTED for a case skip it.  Returns the number of
+    (form, case) pairs that ran per form."""
+    from tensorium_amd._abi import TnsError
+    ran = [0] * nv
+    for v in range(nv):
+        select(v)
+        for i, case in enumerate(cases):
+            sq, W = _sq(case)
+            try:
+                got, ref = _dx_case(hip, torch, ora, *sq, seed=seed0 + i, W=W)
+            except TnsError:
+                continue
+            ran[v] += 1
+            assert np.array_equal(got, ref), (v, case)
+    return ran
+
+
+def test_conv_backward_dx_tiles_nonsquare(hip, torch_cuda, ora):
+    nv = hip.convDxTiles()
+    hip.setDxFused(0)
+    try:
+        ran = _forced_dx_forms(hip, torch_cuda, ora, nv, hip.setDxTile, DX_NS, 150)
+    finally:
+        hip.setDxTile(-1)
+        hip.setDxFused(1)
+    assert min(ran) >= 2, str(ran)
+
+
+def test_conv_backward_dx_conv_forms_nonsquare(hip, torch_cuda, ora):
+    nv = hip.convDxConvs()
+    try:
+        ran = _forced_dx_forms(hip, torch_cuda, ora, nv, hip.setDxConv, DX3_NS, 180)
+    finally:
+        hip.setDxConv(-1)
+    assert min(ran) >= 2, str(ran)
+
+
+def test_conv_backward_dx_conv_stride2_forms_nonsquare(hip, torch_cuda, ora):
+    nv = hip.convDxConvs()
+    try:
+        ran = _forced_dx_forms(hip, torch_cuda, ora, nv, hip.setDxConv, DX3S2_NS, 220)
+    finally:
+        hip.setDxConv(-1)
+    assert min(ran) >= 2, str(ran)
 
 
 @pytest.mark.parametrize("idx", [2, 28, 45])
@@ -544,12 +727,13 @@ DW_CASES = [(2, 64, 13, 64, 3, 1, 1, 9), (3, 128, 9, 64, 1, 1, 0, 4), (1, 64, 17
 
 
 def _dw_case(hip, torch, ora, batch, C, H, F, k, s, p, act, seed, dil=1, state_delta=False,
-             workspace=False):
+             workspace=False, W=None):
+    W = H if W is None else W
     rng = np.random.default_rng(seed)
-    oh = ora.out_dim(H, p * dil, k, dil, s)
-    x = rng.uniform(-1, 1, (batch, C, H, H)).astype(np.float32)
+    oh, ow = ora.out_dim(H, p * dil, k, dil, s), ora.out_dim(W, p * dil, k, dil, s)
+    x = rng.uniform(-1, 1, (batch, C, H, W)).astype(np.float32)
     w = rng.uniform(-0.3, 0.3, F * C * k * k).astype(np.float32)
-    out = rng.uniform(-1, 1, (batch, F, oh, oh)).astype(np.float32)
+    out = rng.uniform(-1, 1, (batch, F, oh, ow)).astype(np.float32)
     d0 = rng.uniform(-1, 1, out.shape).astype(np.float32)
     bu0 = rng.uniform(-1, 1, F).astype(np.float32)
     wu0 = rng.uniform(-1, 1, F * C * k * k).astype(np.float32)
@@ -560,12 +744,13 @@ def _dw_case(hip, torch, ora, batch, C, H, F, k, s, p, act, seed, dil=1, state_d
     t = lambda a: torch.from_numpy(a.copy()).cuda()  # noqa: E731
     dx, dw, dout, dd, dbu, dwu = map(t, (x, w, out, d0, bu0, wu0))
     dsd = t(sd0) if state_delta else None
-    ws = torch.zeros(batch * C * k * k * oh * oh, device="cuda") if workspace else None
-    hip.convBackward(batch, C, H, H, dx, dw, F, k, s, p, dil, act, dout, dd, dbu, dwu, ws, dsd)
+    ws = torch.zeros(batch * C * k * k * oh * ow, device="cuda") if workspace else None
+    hip.convBackward(batch, C, H, W, dx, dw, F, k, s, p, dil, act, dout, dd, dbu, dwu, ws, dsd)
     hip.finish()
     if state_delta:
         assert np.array_equal(dsd.cpu().numpy(), rsd), "state_delta"
         assert np.array_equal(dbu.cpu().numpy(), rbu), "bias_updates"
+        assert np.array_equal(dd.cpu().numpy(), rd), "delta"
     return dwu.cpu().numpy(), rwu
 
 
@@ -700,6 +885,105 @@ def test_conv_backward_dw_rc_forms(hip, torch_cuda, ora, idx):
         hip.setSdotForm(-1)
 
 
+DW_NS = _nonsquare([(2, 64, 13, 20, 64, 3, 1, 1, 9), (3, 128, 9, 14, 64, 1, 1, 0, 4),
+                    (2, 16, 20, 13, 64, 3, 2, 1, 9), (9, 64, 12, 7, 64, 3, 1, 1, 9),
+                    # 128 filters: the tiles of 128 filter rows
+                    (1, 64, 17, 10, 128, 3, 1, 1, 1), (2, 128, 11, 16, 128, 3, 1, 1, 9)])
+# the backward pads with p * dil (nConvolutionLayer.pas:640)
+DWR_NS = _nonsquare([(3, 128, 11, 16, 128, 3, 1, 1, 9), (2, 64, 20, 13, 128, 3, 2, 1, 1),
+                     (2, 64, 9, 14, 64, 1, 1, 0, 4), (2, 128, 10, 15, 128, 3, 1, 1, 9, 2),
+                     (1, 16, 72, 40, 64, 3, 1, 1, 9)],
+                    geo=lambda c: (c[5], c[6], c[7] * (c[9] if len(c) > 9 else 1),
+                                   c[9] if len(c) > 9 else 1))
+# YOLOv3 layers 45 and 58 (13^2 at batch 8) with W about half of H
+DW_RC_NS = _nonsquare([(8, 512, 13, 7, 1024, 3, 1, 1, 9), (8, 1024, 13, 6, 255, 1, 1, 0, 4)])
+
+
+def test_conv_backward_dw_tiles_nonsquare(hip, torch_cuda, ora):
+    from tensorium_amd._abi import TnsError
+    nv = hip.convDwTiles()
+    ran = [0] * nv
+    try:
+        for v in range(nv):
+            hip.setDwTile(v)
+            for i, case in enumerate(DW_NS):
+                sq, W = _sq(case)
+                try:
+                    got, ref = _dw_case(hip, torch_cuda, ora, *sq, seed=170 + i, W=W)
+                except TnsError:
+                    continue
+                ran[v] += 1
+                assert np.array_equal(got, ref), (v, case)
+    finally:
+        hip.setDwTile(-1)
+    assert min(ran) >= 2, str(ran)
+
+
+def test_conv_backward_dw_res_forms_nonsquare(hip, torch_cuda, ora):
+    from tensorium_amd._abi import TnsError
+    nv = hip.convDwRes()
+    ran = [0] * nv
+    try:
+        for v in range(nv):
+            hip.setDwRes(v)
+            for i, case in enumerate(DWR_NS):
+                sq, W = _sq(case)
+                dil = sq[8] if len(sq) > 8 else 1
+                try:
+                    got, ref = _dw_case(hip, torch_cuda, ora, *sq[:8], seed=190 + i, dil=dil,
+                                        state_delta=i % 2 == 0, W=W)
+                except TnsError:
+                    continue
+                ran[v] += 1
+                assert np.array_equal(got, ref), (v, case)
+    finally:
+        hip.setDwRes(-1)
+    assert min(ran) >= 2, str(ran)
+
+
+@pytest.mark.parametrize("overlap", [1, 0])
+def test_conv_backward_caller_workspace_nonsquare(hip, torch_cuda, ora, overlap):
+    batch, C, H, W, F, k, s, p, act = _nonsquare([(4, 32, 19, 12, 64, 3, 1, 1, 9)])[0]
+    try:
+        hip.setBwdOverlap(bool(overlap))
+        hip.setDwTile(-2)   # dW reads an im2col matrix: both chains need a col buffer
+        got, ref = _dw_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, seed=193,
+                            state_delta=True, workspace=True, W=W)
+        assert np.array_equal(got, ref)
+    finally:
+        hip.setBwdOverlap(True)
+        hip.setDwTile(-1)
+
+
+@pytest.mark.parametrize("case", DW_RC_NS)
+def test_conv_backward_dw_rc_forms_nonsquare(hip, torch_cuda, ora, case):
+    batch, C, H, W, F, k, s, p, act = case
+    rng = np.random.default_rng(200 + C)
+    oh, ow = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    x = rng.uniform(-1, 1, (batch, C, H, W)).astype(np.float32)
+    w = rng.uniform(-0.1, 0.1, F * C * k * k).astype(np.float32)
+    out = rng.uniform(-1, 1, (batch, F, oh, ow)).astype(np.float32)
+    d0 = rng.uniform(-1, 1, out.shape).astype(np.float32)
+    bu0 = rng.uniform(-1, 1, F).astype(np.float32)
+    wu0 = rng.uniform(-1, 1, F * C * k * k).astype(np.float32)
+    rd, rbu, rwu = d0.copy(), bu0.copy(), wu0.copy()
+    ora.conv_backward(x, w, F, k, s, p, act, out, rd, rbu, rwu, None)
+    t = lambda a: torch_cuda.from_numpy(a.copy()).cuda()  # noqa: E731
+    dx, dw, dout = map(t, (x, w, out))
+    try:
+        for v in range(hip.sdotRcVariants()):
+            hip.setSdotForm(64 + v)
+            dd, dbu, dwu = map(t, (d0, bu0, wu0))
+            hip.convBackward(batch, C, H, W, dx, dw, F, k, s, p, 1, act, dout, dd, dbu, dwu)
+            hip.finish()
+            got = dwu.cpu().numpy()
+            assert np.array_equal(got, rwu), (v, float(np.abs(got - rwu).max()))
+            assert np.array_equal(dd.cpu().numpy(), rd)
+            assert np.array_equal(dbu.cpu().numpy(), rbu)
+    finally:
+        hip.setSdotForm(-1)
+
+
 @pytest.mark.parametrize("fused", [2, 0])
 @pytest.mark.parametrize("batch,C,H,F,k,s,p,act", [
     (2, 8, 17, 12, 3, 1, 1, 9), (3, 64, 13, 100, 3, 1, 1, 1), (2, 68, 9, 40, 1, 1, 0, 4),
@@ -738,6 +1022,27 @@ def test_conv_backward_state_delta_fused(hip, torch_cuda, ora, fused, batch, C, 
     assert np.array_equal(dd.cpu().numpy(), rd)
 
 
+FUSED_DX_NS = _nonsquare([
+    (2, 8, 17, 11, 12, 3, 1, 1, 9), (3, 64, 13, 8, 100, 3, 1, 1, 1), (2, 68, 9, 14, 40, 1, 1, 0, 4),
+    (1, 32, 20, 9, 16, 5, 1, 2, 9), (2, 16, 11, 6, 24, 3, 1, 0, 9), (1, 132, 7, 12, 65, 3, 1, 1, 0),
+    (8, 512, 13, 7, 1024, 3, 1, 1, 9), (8, 128, 52, 20, 256, 3, 1, 1, 9),
+    (8, 32, 208, 100, 64, 3, 1, 1, 9)])
+
+
+@pytest.mark.parametrize("fused", [2, 0])
+@pytest.mark.parametrize("case", FUSED_DX_NS)
+def test_conv_backward_state_delta_fused_nonsquare(hip, torch_cuda, ora, fused, case):
+    sq, W = _sq(case)
+    hip.setDxFused(fused)
+    try:
+        got, ref = _bwd_case(hip, torch_cuda, ora, *sq, seed=sq[1] * 7 + sq[3] + sq[2], W=W,
+                             neg_zero=True)
+    finally:
+        hip.setDxFused(1)
+    for n, g, r in zip(("delta", "state_delta", "weight_updates", "bias_updates"), got, ref):
+        assert np.array_equal(g, r), n
+
+
 def _t(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()
 
@@ -762,9 +1067,36 @@ def test_conv_train_batchnorm_forward_backward(hip, torch_cuda, ora, batch, C, H
     batchNormBack, bit-exact: output, x, x_norm, mean, variance, rolling
     statistics; delta, scale_updates, mean/variance_delta, weight_updates,
     state_delta — with and without the srss / sVarinceDelta lane drop."""
+    _bn_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, dil, quirk)
+
+
+# H != W planes; the chain kernels of batchnorm.hip change form at plane
+# sizes 256, 4096 and 16384 (bs < 256, bs >= 4096, bs >= 16384), edges that
+# only non-square planes hit exactly
+BN_NS = _nonsquare([
+    (2, 3, 17, 10, 8, 3, 1, 1, 9, 1), (3, 5, 12, 19, 7, 3, 2, 1, 9, 1),
+    (2, 16, 9, 13, 5, 1, 1, 0, 4, 1), (2, 4, 15, 11, 6, 3, 1, 1, 9, 2),
+    (2, 3, 15, 17, 5, 3, 1, 1, 9, 1),     # 255 pixels
+    (1, 2, 63, 65, 3, 3, 1, 1, 9, 1),     # 4095
+    (1, 2, 17, 241, 3, 3, 1, 1, 9, 1),    # 4097
+    (1, 1, 127, 129, 2, 3, 1, 1, 9, 1),   # 16383
+    (1, 1, 113, 145, 2, 3, 1, 1, 9, 1),   # 16385
+    (1, 1, 64, 256, 2, 3, 1, 1, 9, 1)])   # 16384, a multiple of 8: the lane drop matters
+assert [c[2] * c[3] for c in BN_NS[4:]] == [255, 4095, 4097, 16383, 16385, 16384]
+
+
+@pytest.mark.parametrize("quirk", [0, 1])
+@pytest.mark.parametrize("case", BN_NS)
+def test_conv_train_batchnorm_forward_backward_nonsquare(hip, torch_cuda, ora, case, quirk):
+    batch, C, H, W, F, k, s, p, act, dil = case
+    _bn_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, dil, quirk, W=W)
+
+
+def _bn_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, dil, quirk, W=None):
     T = torch_cuda
+    W = H if W is None else W
     rng = np.random.default_rng(batch * 7 + C + H + dil)
-    x = rng.uniform(-1, 1, (batch, C, H, H)).astype(np.float32)
+    x = rng.uniform(-1, 1, (batch, C, H, W)).astype(np.float32)
     w = rng.uniform(-0.3, 0.3, F * C * k * k).astype(np.float32)
     sc = rng.uniform(0.5, 1.5, F).astype(np.float32)
     b = rng.uniform(-0.2, 0.2, F).astype(np.float32)
@@ -777,7 +1109,7 @@ def test_conv_train_batchnorm_forward_backward(hip, torch_cuda, ora, batch, C, H
          (("out", out), ("m", m), ("v", v), ("xs", xs), ("xn", xn))}
     hip.setSrssQuirk(bool(quirk))
     try:
-        hip.convForwardTrain(batch, C, H, H, dx, dw, F, k, s, p, dil, act, dsc, db, drm, drv, 0.1,
+        hip.convForwardTrain(batch, C, H, W, dx, dw, F, k, s, p, dil, act, dsc, db, drm, drv, 0.1,
                              True, g["m"], g["v"], g["xs"], g["xn"], None, g["out"])
         hip.finish()
         for n, r in (("out", out), ("m", m), ("v", v), ("xs", xs), ("xn", xn)):
@@ -787,7 +1119,8 @@ def test_conv_train_batchnorm_forward_backward(hip, torch_cuda, ora, batch, C, H
         # dilation, nConvolutionLayer.pas:92-100), which differs from the
         # dilated forward's rows — the reference's dilated layer cannot run
         # forward and backward on one tensor, so that case stops here
-        if ora.lib().ora_conv_backward_oh(H, k, s, p, dil) != out.shape[2]:
+        if (ora.lib().ora_conv_backward_oh(H, k, s, p, dil) != out.shape[2] or
+                ora.lib().ora_conv_backward_oh(W, k, s, p, dil) != out.shape[3]):
             return
         d0 = rng.uniform(-1, 1, out.shape).astype(np.float32)
         su0 = rng.uniform(-1, 1, F).astype(np.float32)
@@ -798,7 +1131,7 @@ def test_conv_train_batchnorm_forward_backward(hip, torch_cuda, ora, batch, C, H
                                       rsd, dil=dil, quirk=quirk)
         dd, dsu, dwu, dsd = (_t(T, a) for a in (d0, su0, wu0, sd0))
         dmd, dvd = T.zeros(F, device="cuda"), T.zeros(F, device="cuda")
-        hip.convBackwardBN(batch, C, H, H, dx, dw, F, k, s, p, dil, act, _t(T, out), dd, dsc,
+        hip.convBackwardBN(batch, C, H, W, dx, dw, F, k, s, p, dil, act, _t(T, out), dd, dsc,
                            _t(T, xs), _t(T, xn), _t(T, m), _t(T, v), dsu, dmd, dvd, dwu, None, dsd)
         hip.finish()
     finally:
@@ -878,6 +1211,13 @@ def test_conv_backward_dilation_same_padding(hip, torch_cuda, ora):
     hip.finish()
     for gg, r in ((dd, rd), (dbu, rbu), (dwu, rwu), (dsd, rsd)):
         assert np.array_equal(gg.cpu().numpy(), r)
+
+
+def test_conv_backward_dilation_same_padding_nonsquare(hip, torch_cuda, ora):
+    batch, C, H, W, F, k, s, p, d = 2, 3, 14, 9, 5, 3, 1, 1, 2
+    got, ref = _dw_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, 9, seed=22, dil=d,
+                        state_delta=True, W=W)   # (state_delta and bias_updates checked inside)
+    assert np.array_equal(got, ref)
 
 
 def test_conv_backward_rejects_dilation(hip, torch_cuda):
@@ -1004,3 +1344,135 @@ def test_conv1x1_forms_bit_exact(hip, torch_cuda, ora):
     finally:
         hip.setConvVariant(-1)
     assert ran >= 6 * nv
+
+
+TILE_NS = _nonsquare([
+    (2, 32, 17, 29, 128, 3, 1, 1, 9, 1), (3, 32, 12, 21, 64, 3, 2, 1, 9, 1),
+    (2, 64, 9, 14, 32, 1, 1, 0, 4, 1), (1, 96, 26, 11, 128, 3, 2, 1, 1, 1),
+    (2, 32, 21, 12, 64, 3, 1, 2, 9, 2), (2, 64, 13, 20, 128, 3, 1, 1, 9, 1),
+    (1, 128, 11, 18, 256, 3, 2, 1, 1, 1), (2, 128, 9, 6, 128, 1, 1, 0, 4, 1)])
+SLAB_NS = _nonsquare([
+    (3, 64, 7, 12, 128, 3, 1, 1, 1), (2, 16, 9, 5, 64, 3, 1, 1, 4), (1, 128, 5, 8, 64, 1, 1, 0, 0),
+    (8, 256, 26, 13, 512, 3, 1, 1, 9), (8, 256, 26, 15, 1024, 3, 2, 1, 9)])
+C1_NS = _nonsquare([(3, 64, 6, 10, 48, 1), (1, 32, 2, 6, 16, 0), (2, 128, 10, 6, 40, 9),
+                    (8, 256, 52, 20, 128, 9), (8, 512, 26, 10, 255, 4)],
+                   geo=lambda c: (1, 1, 0, 1))
+# 70 pixels per plane, not a multiple of 4: every 1x1 form must refuse it
+C1_NS_RAGGED = _nonsquare([(2, 128, 10, 7, 40, 9)], geo=lambda c: (1, 1, 0, 1))
+
+
+def _forced_conv_forms(hip, torch, ora, nv, base, cases, seed0):
+    """Every case on every forced forward form base + v (fused = 3), as the
+    square tests: a form that reports UNSUPPORTED for a case skips it.
+    Returns how many cases ran on each form."""
+    from tensorium_amd._abi import TnsError
+    ran = [0] * nv
+    try:
+        for v in range(nv):
+            hip.setConvVariant(base + v)
+            for i, case in enumerate(cases):
+                batch, C, H, W, F, k, s, p, act = case[:9]
+                d = case[9] if len(case) > 9 else 1
+                try:
+                    got, ref = conv_case(hip, torch, ora, batch, C, H, F, k, s, p, act, 3,
+                                         seed=seed0 + i, dil=d, W=W)
+                except TnsError:
+                    continue
+                ran[v] += 1
+                assert np.array_equal(got, ref), (base + v, case)
+    finally:
+        hip.setConvVariant(-1)
+    return ran
+
+
+def test_conv_tile_variants_nonsquare(hip, torch_cuda, ora):
+    ran = _forced_conv_forms(hip, torch_cuda, ora, hip.convTileVariants(), 100, TILE_NS, 300)
+    assert min(ran) >= 2, str(ran)
+
+
+def test_conv_slab_forms_nonsquare(hip, torch_cuda, ora):
+    ran = _forced_conv_forms(hip, torch_cuda, ora, hip.convSlabForms(), 500, SLAB_NS, 340)
+    assert min(ran) >= 2, str(ran)
+
+
+def test_conv1x1_forms_nonsquare(hip, torch_cuda, ora):
+    cases = [(b, C, H, W, F, 1, 1, 0, act) for b, C, H, W, F, act in C1_NS]
+    ran = _forced_conv_forms(hip, torch_cuda, ora, hip.conv1x1Forms(), 600, cases, 370)
+    assert min(ran) >= 2, str(ran)
+    ragged = [(b, C, H, W, F, 1, 1, 0, act) for b, C, H, W, F, act in C1_NS_RAGGED]
+    ran = _forced_conv_forms(hip, torch_cuda, ora, hip.conv1x1Forms(), 600, ragged, 380)
+    assert max(ran) == 0, ran
+
+
+@pytest.mark.parametrize("case", [SMALL_NS[0], IMPLICIT_NS[2], DIRECT_NS[1], TILE_NS[5], SLAB_NS[3],
+                                  C1_NS[3][:5] + (1, 1, 0) + C1_NS[3][5:]])
+def test_conv_forward_default_choice_nonsquare(hip, torch_cuda, ora, case):
+    """fused = 1 with no option set: the pickers' own choice on H != W planes,
+    one case from each forced list above."""
+    batch, C, H, W, F, k, s, p, act = case[:9]
+    d = case[9] if len(case) > 9 else 1
+    got, ref = conv_case(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act, 1, seed=11, dil=d,
+                         W=W)
+    assert np.array_equal(got, ref), case
+
+
+# ---- tns_hip_conv2d per axis ------------------------------------------------
+CONV2D_NS = [  # batch, C, H, W, F, kH, kW, wPad, hPad, xStride, yStride, dil
+    (2, 6, 15, 10, 9, 3, 2, 0, 1, 2, 1, 1), (2, 4, 9, 16, 5, 1, 3, 2, 0, 1, 2, 1),
+    (1, 3, 12, 20, 4, 2, 3, 1, 1, 1, 1, 2),
+    # negative paddings: the reference's default, dilation + k div 2 - 1
+    (2, 3, 11, 16, 4, 3, 5, -1, -1, 1, 1, 1), (1, 4, 13, 8, 6, 3, 3, -1, 0, 1, 2, 2),
+    # 1x1 / stride 1 / dilation 1 skips im2col (ntensors.pas:8286-8312): a
+    # non-zero padding still sizes the output (9 x 14) but the product reads C
+    # rows of 126 floats straight from the unpadded planes, 630 floats per
+    # 420-float image; the last image's come from the spare image that
+    # _conv2d_case keeps behind the batch
+    (2, 5, 7, 12, 6, 1, 1, 1, 1, 1, 1, 1)]
+for _c in CONV2D_NS:
+    assert _c[2] != _c[3], _c
+assert 5 * 9 * 14 <= 2 * 5 * 7 * 12   # the over-read stays inside the spare image
+
+
+def _conv2d_case(hip, torch, ora, batch, C, H, W, F, kH, kW, wP, hP, xS, yS, dil, seed=0):
+    # one spare image behind the batch, on both sides: what the no-im2col
+    # path reads past the last image is inside the buffer and the same bits
+    xfull = ora.uniform((batch + 1) * C * H * W, 3, 400 + seed).reshape(batch + 1, C, H, W)
+    w = ora.uniform(F * C * kH * kW, 4, 400 + seed, -0.2, 0.2)
+    ref = ora.conv2d(xfull[:batch], w, F, kH=kH, kW=kW, wPad=wP, hPad=hP, xStride=xS, yStride=yS,
+                     dil=dil)
+    out = torch.full(ref.shape, float("nan"), device="cuda")
+    hip.conv2d(batch, C, H, W, torch.from_numpy(xfull).cuda(), torch.from_numpy(w).cuda(), F, kH,
+               kW, wP, hP, xS, yS, dil, dil, None, out)
+    hip.finish()
+    return out.cpu().numpy(), ref
+
+
+@pytest.mark.parametrize("case", CONV2D_NS)
+def test_conv2d_per_axis_matches_oracle(hip, torch_cuda, ora, case):
+    got, ref = _conv2d_case(hip, torch_cuda, ora, *case, seed=sum(case))
+    assert ref.shape[2] != ref.shape[3] and ref.size > 0
+    assert np.array_equal(got, ref), case
+
+
+@pytest.mark.parametrize("H,W,xDil,yDil", [(12, 20, 1, 2), (12, 20, 2, 1), (12, 12, 1, 2)])
+def test_conv2d_refuses_unequal_dilations(hip, torch_cuda, ora, H, W, xDil, yDil):
+    """xDilation != yDilation: the reference's swapped im2col slots give a
+    column grid other than oH x oW (it runs past its workspace); status 4
+    before anything is launched, out untouched, and the context works on."""
+    from tensorium_amd._abi import TnsError
+    batch, C, F, k = 2, 3, 4, 3
+    x = ora.uniform(batch * C * H * W, 3, 500).reshape(batch, C, H, W)
+    w = ora.uniform(F * C * k * k, 4, 500, -0.2, 0.2)
+    dx, dw = torch_cuda.from_numpy(x).cuda(), torch_cuda.from_numpy(w).cuda()
+    oh, ow = H - yDil * (k - 1), W - xDil * (k - 1)
+    out = torch_cuda.full((batch, F, oh, ow), 7.5, device="cuda")
+    hip.finish()
+    with pytest.raises(TnsError, match=r"tns status 4: .*\d+x\d+ im2col columns.*%dx%d" % (oh, ow)):
+        hip.conv2d(batch, C, H, W, dx, dw, F, k, k, 0, 0, 1, 1, xDil, yDil, None, out)
+    hip.finish()
+    assert bool((out == 7.5).all())
+    ref = ora.conv2d(x, w, F, k, 0, 1, 2)
+    out2 = torch_cuda.full(ref.shape, float("nan"), device="cuda")
+    hip.conv2d(batch, C, H, W, dx, dw, F, k, k, 0, 0, 1, 1, 2, 2, None, out2)
+    hip.finish()
+    assert np.array_equal(out2.cpu().numpy(), ref)

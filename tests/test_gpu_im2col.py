@@ -59,6 +59,93 @@ def test_col2im_bit_exact(hip, torch_cuda, ora, geo, batch):
     assert np.array_equal(dim.cpu().numpy(), ref)
 
 
+# per-axis windows: kH != kW, padH != padW, sY != sX, dY != dX on H != W
+# planes.  (4,12,9, 3,3, ..., 2,1, ...) is a 3x3 window with sY != sX: col2im
+# takes col2im_fast_kernel<0> (runtime strides), not the k3 kernels;
+# (2,8,15, 3,3, 2,0, 1,1, 1,2) takes col2im_k3_kernel<1> with dY != dX.
+ANISO_GEOS = [  # C, H, W, kH, kW, padH, padW, sY, sX, dY, dX
+    (3, 9, 14, 3, 2, 1, 0, 1, 2, 1, 1), (2, 11, 8, 1, 3, 0, 2, 2, 1, 1, 2),
+    (2, 10, 13, 2, 3, 1, 1, 3, 1, 2, 1), (1, 7, 16, 3, 1, 0, 0, 1, 3, 2, 1),
+    (4, 12, 9, 3, 3, 1, 1, 2, 1, 1, 1), (2, 8, 15, 3, 3, 2, 0, 1, 1, 1, 2),
+]
+
+
+def _out_dim(inp, pad, k, dil, stride):   # oracle.out_dim (Pascal div truncates toward zero)
+    v = inp + 2 * pad - (dil * (k - 1) + 1)
+    q = abs(v) // stride
+    return (q if v >= 0 else -q) + 1
+
+
+for _g in ANISO_GEOS:
+    _C, _H, _W, _kH, _kW, _pH, _pW, _sY, _sX, _dY, _dX = _g
+    _oh, _ow = _out_dim(_H, _pH, _kH, _dY, _sY), _out_dim(_W, _pW, _kW, _dX, _sX)
+    assert _H != _W and _oh != _ow and _oh > 0 and _ow > 0, _g
+    assert (_kH, _pH, _sY, _dY) != (_kW, _pW, _sX, _dX), _g
+
+
+@pytest.mark.parametrize("geo", ANISO_GEOS)
+@pytest.mark.parametrize("batch", [1, 3])
+def test_im2col_per_axis_bit_exact(hip, torch_cuda, ora, geo, batch):
+    C, H, W = geo[:3]
+    x = ora.uniform(batch * C * H * W, 3, 100 + sum(geo))
+    ref = ora.im2col(*geo, x, batch=batch)
+    dx = torch_cuda.from_numpy(x).cuda()
+    dcol = torch_cuda.full(ref.shape, float("nan"), device="cuda")
+    hip.im2colStridedBatched(*geo, dx, C * H * W, 0, dcol, ref[0].size, 0, batch)
+    hip.finish()
+    assert dcol.cpu().numpy().tobytes() == ref.tobytes()
+
+
+@pytest.mark.parametrize("geo", ANISO_GEOS)
+@pytest.mark.parametrize("batch", [1, 2])
+def test_col2im_per_axis_bit_exact(hip, torch_cuda, ora, geo, batch):
+    C, H, W, kH, kW, pH, pW, sY, sX, dY, dX = geo
+    oh, ow = ora.out_dim(H, pH, kH, dY, sY), ora.out_dim(W, pW, kW, dX, sX)
+    col = ora.uniform(batch * C * kH * kW * oh * ow, 4, 100 + sum(geo))
+    base = ora.uniform(batch * C * H * W, 5, 100 + sum(geo))
+    ref = ora.col2im(*geo, col.copy(), base.copy(), batch=batch)
+    dcol = torch_cuda.from_numpy(col).cuda()
+    dim = torch_cuda.from_numpy(base.copy()).cuda()
+    hip.col2imStridedBatched(*geo, dcol, col.size // batch, 0, dim, C * H * W, 0, batch)
+    hip.finish()
+    assert np.array_equal(dim.cpu().numpy(), ref)
+
+
+# The plain im2col_kernel<VEC> of launch_im2col, taken when the row-staged
+# form's R rows of Wp = W + 2*pad floats do not fit 64 KB of LDS:
+#  (2,4,4200,3,1,1,1): oh x ow = 4 x 4200, ohw = 16800 (a multiple of 4: the
+#    float4 form); R = max(1, 4096 / 4200) = 1 < oh, rounded up to 4 rows;
+#    4 * 4202 * 4 = 67232 bytes > 65536  => im2col_kernel<4>
+#  (1,3,16390,3,1,1,1): oh x ow = 3 x 16390, ohw = 49170 (not a multiple of 4:
+#    the scalar form); R = max(1, 2048 / 16390) = 1 < oh; 1 * 16392 * 4 =
+#    65568 bytes > 65536  => im2col_kernel<1>
+WIDE_GEOS = [(2, 4, 4200, 3, 1, 1, 1), (1, 3, 16390, 3, 1, 1, 1)]
+
+for _C, _H, _W, _k, _p, _s, _d in WIDE_GEOS:
+    _oh, _ow = _out_dim(_H, _p, _k, _d, _s), _out_dim(_W, _p, _k, _d, _s)
+    _vec = (_oh * _ow) % 4 == 0
+    _R = max(1, (4096 if _vec else 2048) // _ow)
+    assert _R < _oh
+    if _vec:
+        _R = max(4, _R & ~3)
+    assert _R * (_W + 2 * _p) * 4 > 64 * 1024, (_C, _H, _W)
+assert (4 * 4200) % 4 == 0 and (3 * 16390) % 4 != 0
+
+
+@pytest.mark.parametrize("geo", WIDE_GEOS)
+@pytest.mark.parametrize("batch", [1, 3])
+def test_im2col_wide_rows_plain_kernel(hip, torch_cuda, ora, geo, batch):
+    C, H, W, k, p, s, d = geo
+    x = ora.uniform(batch * C * H * W, 3, 200 + C)
+    ref = ora.im2col(C, H, W, k, k, p, p, s, s, d, d, x, batch=batch)
+    dx = torch_cuda.from_numpy(x).cuda()
+    dcol = torch_cuda.full(ref.shape, float("nan"), device="cuda")
+    hip.im2colStridedBatched(C, H, W, k, k, p, p, s, s, d, d, dx, C * H * W, 0, dcol,
+                             ref[0].size, 0, batch)
+    hip.finish()
+    assert dcol.cpu().numpy().tobytes() == ref.tobytes()
+
+
 def test_host_api_im2col_col2im(hiplib, torch_cuda, ora):
     from tensorium_amd.ntensors import bind_hip_op_table
     ops = bind_hip_op_table()
@@ -88,3 +175,23 @@ def test_im2col_yolo_first_layer_full_size(hip, torch_cuda, ora):
                              ref[0].size, 0, batch)
     hip.finish()
     assert dcol.cpu().numpy().tobytes() == ref.tobytes()
+
+
+def test_host_api_im2col_col2im_per_axis(hiplib, torch_cuda, ora):
+    from tensorium_amd.ntensors import bind_hip_op_table
+    ops = bind_hip_op_table()
+    geo = (3, 9, 14, 3, 2, 1, 0, 1, 2, 1, 1)
+    C, H, W = geo[:3]
+    batch = 2
+    x = ora.uniform(batch * C * H * W, 6, 1)
+    ref = ora.im2col(*geo, x, batch=batch)
+    col = np.zeros_like(ref)
+    ops.im2colStridedBatchedvv(*geo, x.ctypes.data, C * H * W, 0, col.ctypes.data, ref[0].size, 0,
+                               batch)
+    assert hiplib.tns_last_error() == b""
+    assert col.tobytes() == ref.tobytes()
+    base = ora.uniform(C * H * W, 7, 1)
+    im = base.copy()
+    ops.col2imvv(*geo, ref[0].ctypes.data, 0, im.ctypes.data, 0, 1, 0)
+    want = ora.col2im(*geo, ref[0].copy(), base.copy())
+    assert np.array_equal(im, want)

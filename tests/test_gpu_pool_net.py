@@ -152,3 +152,44 @@ def test_pool_backward_keeps_the_pipeline_running(hip, torch_cuda, ora):
     assert before >= 1, seen           # the conv above left its dW on the side stream
     assert after >= before, seen       # ... and the pool's backward did not join it
     _compare(net, model, outs, deltas, state, indexes)
+
+
+@pytest.fixture(scope="module")
+def wide(ora):
+    """A 12 x 20 net (batch 2, 16 channels): conv 3x3/1 -> conv 3x3/2 -> conv
+    1x1 -> conv 3x3/1 -> shortcut -3 -> upsample 2 -> route -1,0 -> conv 1x1,
+    and its reference passes (computed once, read only).  Every plane is
+    non-square; the stride-2 layer's 12 x 20 input gives 6 x 10."""
+    conv = ("[convolutional]\nbatch_normalize=1\nfilters={f}\nsize={k}\nstride={s}\npad=1\n"
+            "activation=leaky\n")
+    cfg = ("[net]\nbatch=2\nwidth=20\nheight=12\nchannels=16\n" + conv.format(f=32, k=3, s=1) +
+           conv.format(f=64, k=3, s=2) + conv.format(f=32, k=1, s=1) + conv.format(f=64, k=3, s=1) +
+           "[shortcut]\nfrom=-3\nactivation=linear\n[upsample]\nstride=2\n[route]\nlayers=-1,0\n" +
+           conv.format(f=24, k=1, s=1))
+    net = dn.Network(dn.parse_cfg(cfg))
+    assert [(l.kind, l.out_c, l.out_h, l.out_w) for l in net.layers] == [
+        ("convolutional", 32, 12, 20), ("convolutional", 64, 6, 10), ("convolutional", 32, 6, 10),
+        ("convolutional", 64, 6, 10), ("shortcut", 64, 6, 10), ("upsample", 64, 12, 20),
+        ("route", 96, 12, 20), ("convolutional", 24, 12, 20)]
+    params = dn.random_params(net, seed=75)
+    rng = np.random.default_rng(75)
+    x = rng.uniform(0, 1, (2, 16, 12, 20)).astype(np.float32)
+    top = {7: rng.uniform(-1, 1, 2 * net.layers[7].out_size).astype(np.float32)}
+    return (net, params, x, top, infer_pass(ora, net, params, x),
+            train_pass(ora, net, params, x, [], seed_delta=top))
+
+
+def test_nonsquare_net_forward(hip, torch_cuda, wide):
+    net, params, x, _, ref, _ = wide
+    got = dn.HipDarknet(hip, net, params, torch_cuda).forward(torch_cuda.from_numpy(x).cuda())
+    hip.finish()
+    for l, o, r in zip(net.layers, got, ref):
+        assert np.array_equal(o.cpu().numpy(), r), (l.index, l.kind)
+
+
+@pytest.mark.parametrize("mode", [2, 1])
+def test_nonsquare_net_train_pass(hip, torch_cuda, wide, mode):
+    net, params, x, top, _, (outs, deltas, state, indexes) = wide
+    model = _train(hip, torch_cuda, net, params, x, [], mode, seed_delta=top)
+    assert hip.pendingDw() == 0
+    _compare(net, model, outs, deltas, state, indexes)
