@@ -224,8 +224,9 @@ int tns_hip_col2im_strided_batched(tns_ctx* ctx, int64_t aChannels, int64_t aHei
 int tns_hip_forward_bias(tns_ctx* ctx, int64_t dstSize, float* dst, int64_t offset,
                          int64_t srcSize, const float* src, int64_t incb, int64_t batch);
 
-/* TNNCuda.backwardBias — dst[i] += sum_b sum_j src[(b*dstSize+i)*bs + j]
- * (addSums, ntensors.pas:7729-7781). */
+/* TNNCuda.backwardBias — dst[i*incb] += sum_b sum_j src[(b*dstSize+i)*bs + j]
+ * (addSums, ntensors.pas:7729-7781).  incb >= 1 here and in forwardBias /
+ * forwardScale / forwardScaleAdd (TNS_ERR_ARG otherwise). */
 int tns_hip_backward_bias(tns_ctx* ctx, int64_t dstSize, float* dst, int64_t srcSize,
                           const float* src, int64_t srcOffset, int64_t incb, int64_t batch);
 
@@ -235,7 +236,9 @@ int tns_hip_activate_array(tns_ctx* ctx, int64_t N, float* x, int64_t offset, in
 int tns_hip_derive_array(tns_ctx* ctx, int64_t N, const float* x, int64_t offset,
                          int32_t activation, float* delta);
 
-/* BLAS-1 / elementwise support (TNNCuda.axpy/scale/fill/copy/clamp). */
+/* BLAS-1 / elementwise support (TNNCuda.axpy/scale/fill/copy/clamp).
+ * TNS_ERR_ARG for N < 0, a null operand with N > 0, an increment < 1 on an
+ * operand that is written, or < 0 on one that is only read (0 broadcasts). */
 int tns_hip_axpy(tns_ctx* ctx, int64_t N, float a, const float* x, int64_t xOffset, int64_t incx,
                  float* y, int64_t yOffset, int64_t incy);
 int tns_hip_scale(tns_ctx* ctx, int64_t N, float a, float* x, int64_t stride);
@@ -474,7 +477,10 @@ int tns_hip_normalize_delta(tns_ctx* ctx, int64_t deltaSize, int64_t meanSize, i
 /* addDots: dst[i] += sum x_norm*delta over (group, block) */
 int tns_hip_add_dots(tns_ctx* ctx, int64_t N, int64_t dstSize, int64_t groups,
                      const float* src1, const float* src2, int64_t srcOffset, float* dst);
-/* TSoftmaxLayer.softmaxBatch / softmaxCrossEntropy */
+/* TSoftmaxLayer.softmaxBatch / softmaxCrossEntropy.  softmaxBatch: for every
+ * (b, g), softmax over the N elements every `stride` from
+ * b*batch_size + g*group_size; stride >= 1, the counts and sizes >= 0
+ * (TNS_ERR_ARG otherwise). */
 int tns_hip_softmax_batch(tns_ctx* ctx, int64_t N, const float* input, int64_t iOffset,
                           int64_t batch, int64_t batch_size, int64_t groups, int64_t group_size,
                           int64_t stride, float temp, float* output, int64_t oOffset);

@@ -130,8 +130,11 @@ def col2im(C_, H, W, kH, kW, pH, pW, sY, sX, dY, dX, col: np.ndarray, im: np.nda
     return im
 
 
-def add_bias(x: np.ndarray, bias: np.ndarray, filters: int, block: int, batch: int):
-    lib().ora_add_bias(filters, _p(x), block, _p(bias), 1, batch)
+def add_bias(x: np.ndarray, bias: np.ndarray, filters: int, block: int, batch: int,
+             incb: int = 1):
+    """vsAddB in place: filter f adds bias[f * incb]."""
+    assert incb >= 1 and bias.size >= (filters - 1) * incb + 1, (bias.size, filters, incb)
+    lib().ora_add_bias(filters, _p(x), block, _p(bias), incb, batch)
     return x
 
 
@@ -374,6 +377,26 @@ def softmax_rows(x, n, temp=1.0):
     L = _lib2()
     for r in range(rows):
         L.ora_softmax(n, x.ctypes.data + 4 * r * n, temp, 1, out.ctypes.data + 4 * r * n)
+    return out
+
+
+def softmax_batch(x, n, batch, batch_size, groups, group_size, stride, temp):
+    """TSoftmaxLayer.softmaxBatch (nsoftmaxlayer.pas:108-121): softmax over
+    the n elements every `stride` from x[b*batch_size + g*group_size], for
+    every (b, g).  Returns a copy of x with those elements replaced; the rest
+    (row padding, the elements between the strided ones) stays as it was."""
+    out = x.copy()
+    if n <= 0 or batch <= 0 or groups <= 0:
+        return out
+    assert stride >= 1 and batch_size >= 0 and group_size >= 0
+    last = (batch - 1) * batch_size + (groups - 1) * group_size + (n - 1) * stride
+    assert last < x.size, (last, x.size)
+    L = _lib2()
+    _p(x)
+    for b in range(batch):
+        for g in range(groups):
+            o = 4 * (b * batch_size + g * group_size)
+            L.ora_softmax(n, x.ctypes.data + o, temp, stride, out.ctypes.data + o)
     return out
 
 

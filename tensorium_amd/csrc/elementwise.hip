@@ -152,89 +152,6 @@ __global__ __launch_bounds__(TPB) void backward_bias_kernel(float* __restrict__ 
   if (threadIdx.x == 0) dst[i * incb] = dst[i * incb] + sum;
 }
 
-// Same order for long blocks (conv layers at high resolution): 8 blocks at a
-// time, staged through LDS in tiles of BB_T elements per block by all 256
-// threads (coalesced, double-buffered), while wave 0's 64 lanes (8 per block,
-// the vssum lanes) run the sequential chains out of LDS.  The chains are
-// inherently serial; with one workgroup per output the tile loads' latency
-// bounds the widest layers (32 x 173056 x 8: 0.35 ms, 0.5 TB/s).
-constexpr int BB_T = 1024;
-constexpr int BB_LD = BB_T + 8;  // row stride: the 8 blocks' lanes hit distinct banks
-constexpr int BB_E = 8 * BB_T / TPB;
-__global__ __launch_bounds__(TPB) void backward_bias_tiled_kernel(float* __restrict__ dst,
-                                                                  int64_t nDst,
-                                                                  const float* __restrict__ src,
-                                                                  int64_t bs, int64_t groups,
-                                                                  int64_t incb) {
-  __shared__ float buf[2][8 * BB_LD];
-  __shared__ float tot[8];
-  const int64_t i = blockIdx.x;
-  const int tid = threadIdx.x, jj = (tid & 63) >> 3, l = tid & 7;
-  const bool chain = tid < 64;
-  const int64_t nb8 = (bs >> 3) << 3;  // elements in full 8-blocks
-  const int ntile = (int)((nb8 + BB_T - 1) / BB_T);
-  float sum = 0.0f;
-  for (int64_t j0 = 0; j0 < groups; j0 += 8) {
-    const int jn = groups - j0 < 8 ? (int)(groups - j0) : 8;
-    float r[BB_E];
-    auto load = [&](int t) {
-#pragma unroll
-      for (int u = 0; u < BB_E; ++u) {
-        const int e = tid + TPB * u, b = e / BB_T, x = e % BB_T;
-        const int64_t k = (int64_t)t * BB_T + x;
-        r[u] = (b < jn && k < nb8) ? src[((j0 + b) * nDst + i) * bs + k] : 0.0f;
-      }
-    };
-    auto store = [&](float* d) {
-#pragma unroll
-      for (int u = 0; u < BB_E; ++u) {
-        const int e = tid + TPB * u;
-        d[(e / BB_T) * BB_LD + e % BB_T] = r[u];
-      }
-    };
-    float acc = 0.0f;
-    if (ntile > 0) {
-      load(0);
-      store(buf[0]);
-      __syncthreads();
-    }
-    for (int t = 0; t < ntile; ++t) {
-      if (t + 1 < ntile) load(t + 1);
-      if (chain && jj < jn) {
-        const float* row = buf[t & 1] + jj * BB_LD + l;
-        const int64_t rem = nb8 - (int64_t)t * BB_T;
-        const int cnt = (int)((rem < BB_T ? rem : BB_T) >> 3);
-        int u = 0;
-        for (; u + 16 <= cnt; u += 16) {
-          float v[16];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) v[q] = row[8 * (u + q)];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) acc = acc + v[q];
-        }
-        for (; u < cnt; ++u) acc = acc + row[8 * u];
-      }
-      if (t + 1 < ntile) store(buf[(t + 1) & 1]);
-      __syncthreads();
-    }
-    {
-      const float s = acc + __shfl_down(acc, 4, 8);
-      const float h = s + __shfl_down(s, 1, 8);
-      float q = h + __shfl_down(h, 2, 8);
-      if (chain && l == 0 && jj < jn) {
-        const float* blk = src + ((j0 + jj) * nDst + i) * bs;
-        for (int64_t u = nb8; u < bs; ++u) q = q + blk[u];
-        tot[jj] = q;
-      }
-    }
-    __syncthreads();
-    if (tid == 0)
-      for (int b = 0; b < jn; ++b) sum = sum + tot[b];
-    __syncthreads();
-  }
-  if (tid == 0) dst[i * incb] = dst[i * incb] + sum;
-}
-
 // TConnectedLayer.update / TConvolutionalLayer.update (nconnectedlayer.pas:
 // 324-359, nConvolutionLayer.pas:673-705) in one pass: per weight
 //   u = fma(ndb, w, dw)       weight_updates.axpy(-decay*batch, weights)
@@ -465,12 +382,8 @@ hipError_t launch_derive(const float* x, int64_t n, int act, float* delta, hipSt
 hipError_t launch_backward_bias(float* dst, int64_t nDst, const float* src, int64_t bs,
                                 int64_t batch, int64_t incb, hipStream_t s) {
   if (nDst <= 0) return hipSuccess;
-  if (bs >= 2048)
-    hipLaunchKernelGGL(backward_bias_tiled_kernel, dim3((unsigned)nDst), dim3(TPB), 0, s, dst,
-                       nDst, src, bs, batch, incb);
-  else
-    hipLaunchKernelGGL(backward_bias_kernel, dim3((unsigned)nDst), dim3(TPB), 0, s, dst, nDst,
-                       src, bs, batch, incb);
+  hipLaunchKernelGGL(backward_bias_kernel, dim3((unsigned)nDst), dim3(TPB), 0, s, dst, nDst, src,
+                     bs, batch, incb);
   return hipGetLastError();
 }
 

@@ -1028,6 +1028,7 @@ int tns_hip_forward_bias(tns_ctx* c, int64_t dstSize, float* dst, int64_t offset
                          const float* src, int64_t incb, int64_t batch) {
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, dstSize)}, {span(src, srcSize, incb)}))
     return r;
+  if (incb < 1) return set_error(TNS_ERR_ARG, "forwardBias: incb < 1");
   if (dstSize == 0) return TNS_OK;
   if (!dst || !src || srcSize <= 0 || batch <= 0 || dstSize % (srcSize * batch) != 0)
     return set_error(TNS_ERR_ARG, "forwardBias: sizes do not align");
@@ -1039,13 +1040,17 @@ int tns_hip_forward_bias(tns_ctx* c, int64_t dstSize, float* dst, int64_t offset
 
 int tns_hip_backward_bias(tns_ctx* c, int64_t dstSize, float* dst, int64_t srcSize,
                           const float* src, int64_t srcOffset, int64_t incb, int64_t batch) {
-  if (int r = check_ops(c, {span(dst, dstSize)}, {span(src ? src + srcOffset : nullptr, srcSize)}))
+  if (int r = check_ops(c, {span(dst, dstSize, incb)},
+                        {span(src ? src + srcOffset : nullptr, srcSize)}))
     return r;
+  if (incb < 1) return set_error(TNS_ERR_ARG, "backwardBias: incb < 1");
   if (!dst || !src || dstSize <= 0 || batch <= 0 || srcSize % (dstSize * batch) != 0)
     return set_error(TNS_ERR_ARG, "backwardBias: sizes do not align");
   const int64_t bs = srcSize / (dstSize * batch);
   OpTimer t(c, TNS_OP_BIAS);
-  if (bs == 1 && incb == 1)  // FC layers: the reference's sequential strided sum
+  // FC layers: the reference's sequential strided sum (one output: its
+  // stride-1 sumv, whatever incb says about outputs that do not exist)
+  if (bs == 1 && (incb == 1 || dstSize == 1))
     return hip_status(launch_add_sums(dst, src + srcOffset, batch, dstSize, 1, nullptr, c->stream),
                       "backwardBias launch");
   if (incb == 1 && bs >= 64) {  // conv blocks: lane chains per block
@@ -1084,6 +1089,8 @@ int tns_hip_axpy(tns_ctx* c, int64_t N, float a, const float* x, int64_t xOffset
   if (int r = check_ops(c, {span(y ? y + yOffset : nullptr, N, incy)},
                         {span(x ? x + xOffset : nullptr, N, incx)}))
     return r;
+  if (N < 0 || incx < 0 || incy < 1 || (N > 0 && (!x || !y)))
+    return set_error(TNS_ERR_ARG, "axpy: bad args");
   return hip_status(launch_axpy(N, a, x + xOffset, incx, y + yOffset, incy, c->stream), "axpy");
 }
 
@@ -1106,11 +1113,13 @@ int tns_hip_sgd_update(tns_ctx* c, int64_t nWeights, float* weights, float* weig
 
 int tns_hip_scale(tns_ctx* c, int64_t N, float a, float* x, int64_t stride) {
   if (int r = check_ops(c, {span(x, N, stride)}, {})) return r;
+  if (N < 0 || stride < 1 || (N > 0 && !x)) return set_error(TNS_ERR_ARG, "scale: bad args");
   return hip_status(launch_scale(N, a, x, stride, c->stream), "scale");
 }
 
 int tns_hip_fill(tns_ctx* c, int64_t N, float* x, int64_t offset, float val, int64_t stride) {
   if (int r = check_ops(c, {span(x ? x + offset : nullptr, N, stride)}, {})) return r;
+  if (N < 0 || stride < 1 || (N > 0 && !x)) return set_error(TNS_ERR_ARG, "fill: bad args");
   return hip_status(launch_fill(N, x + offset, val, stride, c->stream), "fill");
 }
 
@@ -1119,6 +1128,8 @@ int tns_hip_copy(tns_ctx* c, int64_t N, const float* src, int64_t srcOffset, int
   if (int r = check_ops(c, {span(dst ? dst + dstOffset : nullptr, N, incb)},
                         {span(src ? src + srcOffset : nullptr, N, inca)}))
     return r;
+  if (N < 0 || inca < 0 || incb < 1 || (N > 0 && (!src || !dst)))
+    return set_error(TNS_ERR_ARG, "copy: bad args");
   return hip_status(launch_copy(N, src + srcOffset, inca, dst + dstOffset, incb, c->stream),
                     "copy");
 }
@@ -1538,6 +1549,8 @@ int tns_hip_clamp(tns_ctx* c, int64_t N, float alpha, const float* src, float* d
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, N, stride)},
                         {span(src ? src + offset : nullptr, N, stride)}))
     return r;
+  if (N < 0 || stride < 1 || (N > 0 && (!src || !dst)))
+    return set_error(TNS_ERR_ARG, "clamp: bad args");
   return hip_status(launch_clamp(N, alpha, src + offset, dst + offset, stride, c->stream),
                     "clamp");
 }
@@ -1624,6 +1637,7 @@ int tns_hip_forward_scale_add(tns_ctx* c, int64_t dstSize, float* dst, int64_t o
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, dstSize)},
                         {span(scales, scaleSize, incb), span(biases, scaleSize, incb)}))
     return r;
+  if (incb < 1) return set_error(TNS_ERR_ARG, "forwardScale: incb < 1");
   int64_t bs;
   if (int r = blocks_of(dstSize, scaleSize, batch, &bs, "forwardScale")) return r;
   if (!dst || !scales) return set_error(TNS_ERR_ARG, "forwardScale: null pointer");
@@ -1691,10 +1705,18 @@ int tns_hip_add_dots(tns_ctx* c, int64_t N, int64_t dstSize, int64_t groups, con
 int tns_hip_softmax_batch(tns_ctx* c, int64_t N, const float* input, int64_t iOffset,
                           int64_t batch, int64_t batch_size, int64_t groups, int64_t group_size,
                           int64_t stride, float temp, float* output, int64_t oOffset) {
-  if (int r = check_ops(c, {span(output ? output + oOffset : nullptr, N)},
-                        {span(input ? input + iOffset : nullptr, N)}))
+  // every (batch, group) row's n strided elements: the last one ends the extent
+  const int64_t ext = (N > 0 && batch > 0 && groups > 0 && batch_size >= 0 && group_size >= 0 &&
+                       stride >= 1)
+                          ? (batch - 1) * batch_size + (groups - 1) * group_size +
+                                (N - 1) * stride + 1
+                          : 0;
+  if (int r = check_ops(c, {span(output ? output + oOffset : nullptr, ext)},
+                        {span(input ? input + iOffset : nullptr, ext)}))
     return r;
-  if (!input || !output || N < 0) return set_error(TNS_ERR_ARG, "softmaxBatch: bad args");
+  if (!input || !output || N < 0 || stride < 1 || batch < 0 || groups < 0 || batch_size < 0 ||
+      group_size < 0)
+    return set_error(TNS_ERR_ARG, "softmaxBatch: bad args");
   return hip_status(launch_softmax_batch(N, input + iOffset, batch, batch_size, groups,
                                          group_size, stride, temp, output + oOffset, c->stream),
                     "softmaxBatch");

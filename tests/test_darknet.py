@@ -126,3 +126,57 @@ def test_upsample_shortcut_yolo_ops(hip, torch_cuda, ora):
     hip.finish()
     r = ora.yolo_forward(y, 2, 3, 80, 13)
     assert np.array_equal(oy.cpu().numpy(), r)
+
+
+G = 16384 * 256  # blocks_for's grid cap x block size: work items of one grid-stride trip
+
+
+@pytest.mark.gpu
+def test_yolo_forward_second_grid_trip(hip, torch_cuda, ora):
+    """yolo_kernel past the grid cap: every element, whole array."""
+    batch, anchors, classes, hw = 1, 3, 2, 199741
+    n = batch * anchors * (classes + 5) * hw
+    assert n > G + 256
+    y = ora.uniform(n, 14, 1, -4.0, 4.0)
+    oy = torch_cuda.full((n,), -77.25, device="cuda")
+    hip.yoloForward(batch, anchors, classes, hw, torch_cuda.from_numpy(y).cuda(), oy)
+    hip.finish()
+    assert np.array_equal(oy.cpu().numpy().view(np.uint32),
+                          ora.yolo_forward(y, batch, anchors, classes, hw).view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("planes,h,w,s", [(13317, 5, 7, 3),      # W*s = 21: upsample_kernel<1>
+                                          (139830, 5, 6, 2)])    # W*s = 12: upsample_kernel<4>
+def test_upsample_forward_second_grid_trip(hip, torch_cuda, ora, planes, h, w, s):
+    T = torch_cuda
+    total = planes * h * s * w * s
+    assert total // (4 if (w * s) % 4 == 0 else 1) > G + 256
+    x = ora.uniform(planes * h * w, 12, s)
+    out = T.full((total,), -77.25, device="cuda")
+    hip.upSample(1, planes, h, w, T.from_numpy(x).cuda(), s, 1, 0.5, out)
+    hip.finish()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32),
+                          ora.upsample(x, planes, h, w, s, 0.5).view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_upsample_backward_second_grid_trip(hip, torch_cuda, ora):
+    """upsample_back_kernel with more input pixels than one trip covers;
+    the reference's order: output row outer, column inner, each product and
+    sum rounded (nupsamplelayer.pas:101-110)."""
+    T = torch_cuda
+    planes, h, w, s = 119850, 5, 7, 2
+    assert planes * h * w > G + 256
+    g = ora.uniform(planes * h * s * w * s, 15, s)
+    base = ora.uniform(planes * h * w, 16, s)
+    dev_in = T.from_numpy(base.copy()).cuda()
+    hip.upSample(1, planes, h, w, dev_in, s, 0, 0.3, T.from_numpy(g).cuda(), 0)
+    hip.finish()
+    ref = base.copy()
+    g4 = g.reshape(planes, h, s, w, s)
+    sc = np.float32(0.3)
+    for dy in range(s):
+        for dx in range(s):
+            ref = (ref + (sc * g4[:, :, dy, :, dx]).reshape(-1)).astype(np.float32)
+    assert np.array_equal(dev_in.cpu().numpy(), ref)

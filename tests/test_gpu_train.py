@@ -368,3 +368,137 @@ def test_bn_null_pointers_are_arg_errors(hip, torch_cuda):
     assert L.tns_hip_variances(hip.ctx, 64, 4, 2, p, 0, None, p) == 1
     assert L.tns_hip_variances(hip.ctx, 63, 4, 2, p, 0, p, p) == 1   # sizes do not align
     hip.finish()
+
+
+# ---- softmaxBatch / crossEntropySoftmax / sum beyond the one contiguous case --
+SENT = np.float32(-77.25)
+
+
+def same(got, ref):
+    """Bit-identical, NaNs matching NaNs of any payload."""
+    nan = np.isnan(ref)
+    return bool(got.shape == ref.shape and np.array_equal(np.isnan(got), nan) and
+                np.array_equal(got.view(np.uint32)[~nan], ref.view(np.uint32)[~nan]))
+
+
+def _softmax_cases():
+    from test_oracle_softmax_batch import SOFTMAX_CASES
+    return SOFTMAX_CASES
+
+
+@pytest.mark.parametrize("case", _softmax_cases())
+def test_softmax_batch_groups_strides_offsets(hip, torch_cuda, ora, case):
+    """TNNCuda.softmaxBatch as the [softmax] layer (groups > 1) and the
+    softmax tree (iOffset = oOffset = count) call it, with stride and
+    temperature live: the (b, g) rows bit-exact against the oracle's loop
+    over ora_softmax, and every other element of the output — row padding,
+    the elements between strided ones, before the offset, past the last row —
+    as it was."""
+    from test_oracle_softmax_batch import softmax_input, softmax_positions
+    n, batch, batch_size, groups, group_size, stride, temp, off = case
+    x = softmax_input(ora, case)
+    ref = ora.softmax_batch(x[off:], n, batch, batch_size, groups, group_size, stride,
+                            float(np.float32(temp)))
+    idx = softmax_positions(n, batch, batch_size, groups, group_size, stride).ravel() + off
+    want = np.full(x.size, SENT, np.float32)
+    want[idx] = ref[idx - off]
+    T = torch_cuda
+    dx, dp = dev(T, x), T.full((x.size,), float(SENT), device="cuda")
+    hip.softmaxBatch(n, dx, off, batch, batch_size, groups, group_size, stride, temp, dp, off)
+    hip.finish()
+    assert same(dp.cpu().numpy(), want)
+    assert same(dx.cpu().numpy(), x), "softmaxBatch wrote to its input"
+
+
+def test_softmax_batch_tiny_exponentials(hip, torch_cuda, ora):
+    """Logits far enough below the row's largest that their exponentials are
+    subnormal floats, or round to 0."""
+    from test_oracle_softmax_batch import tiny_exp_input
+    x = np.concatenate([tiny_exp_input(), tiny_exp_input()[::-1]])
+    n = x.size // 2
+    ref = ora.softmax_batch(x, n, 2, n, 1, 0, 1, 1.0)
+    tiny = np.finfo(np.float32).tiny
+    assert np.any((ref > 0) & (ref < tiny)) and np.any(ref == 0)
+    T = torch_cuda
+    dp = T.full((x.size,), float(SENT), device="cuda")
+    hip.softmaxBatch(n, dev(T, x), 0, 2, n, 1, 0, 1, 1.0, dp, 0)
+    hip.finish()
+    got = dp.cpu().numpy()
+    assert same(got, ref), (got, ref)
+
+
+def _xent_inputs(n):
+    """Every pairing of pred in {1e-30, 0, sEPSILON and its float neighbours,
+    1} with truth in {1, 0, 0.5, -0, NaN}, repeated to n elements."""
+    f32 = np.float32
+    eps = f32(0.000001)
+    pred = np.array([1e-30, 0.0, eps, np.nextafter(eps, f32(0)), np.nextafter(eps, f32(1)), 1.0],
+                    f32)
+    truth = np.array([1.0, 0.0, 0.5, -0.0, np.nan], f32)
+    p, t = (a.ravel() for a in np.meshgrid(pred, truth, indexing="ij"))
+    return np.resize(p, n).astype(f32), np.resize(t, n).astype(f32)
+
+
+@pytest.mark.parametrize("n", [1, 257, 100003])
+def test_cross_entropy_softmax_edges(hip, torch_cuda, ora, n):
+    """softmaxCrossEntropy (nsoftmaxlayer.pas:123-137) where pred is at or
+    below sEPSILON (the floor of the logarithm's argument) and truth is not
+    one-hot: any truth != 0 — 0.5, NaN — takes the logarithm, -0 does not."""
+    p, t = _xent_inputs(n)
+    d, e = ora.softmax_xent(p, t)
+    T = torch_cuda
+    dd, de = T.full((n + 3,), float(SENT), device="cuda"), T.full((n + 3,), float(SENT),
+                                                                  device="cuda")
+    hip.crossEntropySoftmax(n, dev(T, p), dev(T, t), dd, de)
+    hip.finish()
+    pad = np.full(3, SENT, np.float32)
+    assert same(dd.cpu().numpy(), np.concatenate([d, pad])), "delta"
+    assert same(de.cpu().numpy(), np.concatenate([e, pad])), "error"
+
+
+@pytest.mark.parametrize("offset", [0, 3])
+@pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 15, 16, 1029])
+def test_sum_lengths_and_offset(hip, torch_cuda, ora, n, offset):
+    """TNNCuda.sum in vssum_avx2's order: no full 8-block, no tail, both, and
+    an element offset (which also takes the source off 16-byte alignment)."""
+    x = ora.uniform(offset + n + 5, 42, n)
+    T = torch_cuda
+    out = T.full((3,), float(SENT), device="cuda")
+    hip.sum(n, dev(T, x), offset, out[1:])
+    hip.finish()
+    got = out.cpu().numpy()
+    assert got[0] == SENT and got[2] == SENT
+    assert got[1] == np.float32(ora.vssum(np.ascontiguousarray(x[offset:offset + n])))
+
+
+def test_softmax_batch_joins_a_pending_dw_it_reads(hip, torch_cuda, ora):
+    """During a pipelined conv backward (TNS_OPT_BWD_OVERLAP = 2) a call joins
+    the side stream when its operands meet a pending dW's.  softmaxBatch's
+    operands span every (batch, group) row, not the first row alone: a call
+    whose second row lies in the pending weight_updates joins, one whose rows
+    all end before it leaves the dW pending."""
+    T = torch_cuda
+    B, C, H, F, k = 2, 4, 8, 4, 3
+    x = dev(T, ora.uniform(B * C * H * H, 91, 0))
+    w = dev(T, ora.uniform(F * C * k * k, 92, 0, -0.3, 0.3))
+    out = dev(T, ora.uniform(B * F * H * H, 93, 0))
+    lead = 64
+    buf = dev(T, ora.uniform(lead + F * C * k * k, 94, 0))
+    wu = buf[lead:]                      # weight_updates: right behind 64 other floats
+    bu = T.zeros(F, device="cuda")
+    probs = T.zeros(4 * lead, device="cuda")
+    try:
+        hip.setBwdOverlap(2)
+        hip.finish()
+        for rows, joined in ((1, False), (3, True)):
+            delta = dev(T, ora.uniform(B * F * H * H, 95, rows))
+            hip.convBackward(B, C, H, H, x, w, F, k, 1, 1, 1, 9, out, delta, bu, wu, None, None)
+            assert hip.pendingDw() == 1
+            # rows of 8 elements every 64: row 0 in the lead, rows 1.. in weight_updates
+            hip.softmaxBatch(8, buf, 0, rows, lead, 1, 0, 1, 1.0, probs, 0)
+            assert (hip.pendingDw() == 0) == joined, rows
+            hip.finish()
+            assert hip.pendingDw() == 0
+    finally:
+        hip.setBwdOverlap(True)
+        hip.finish()
