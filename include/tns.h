@@ -437,6 +437,44 @@ int tns_hip_lstm_gates_backward(tns_ctx* ctx, int64_t N, const float* wf, const 
                                 float* dc, float* dwf, float* dwi, float* dwg, float* dwo,
                                 float* duf, float* dui, float* dug, float* duo);
 
+/* ---- the elementwise stage of one RNN time step (rnn.hip) ----
+ * Backend-specific fused entries (TNNCuda has none): what
+ * TRNNLayer.rnnStepForward / rnnStepBackward (nrnnlayer.pas:148-216) and the
+ * head of its connected sub-layers' forward / backward (nconnectedlayer.pas:
+ * 157-322) issue as forwardBias, ActivateArray, fill / copy, addvv, clamp,
+ * DeriveArray and copy calls, per element k of the step's N = streams * H
+ * floats.  Every written operation is one float32 rounding; act / grad are
+ * ActivateArray's / DeriveArray's formulas.
+ * tns_hip_rnn_state_forward (in_slice / self_slice: the step's slice of the
+ * input and self sub-layers' output, the NT product only):
+ *   a = in_slice[k];    a = a + in_bias[k % H];    a = act(a, in_act)
+ *   b = self_slice[k];  b = b + self_bias[k % H];  b = act(b, self_act)
+ *   s = (state_prev ? state_prev[k] : 0.0f) + a;   s = s + b
+ *   a -> in_slice[k];  b -> self_slice[k];  s -> state_next[k]
+ * A null bias skips that add (the slice is normalized and biased already:
+ * batch norm).  0.0f + a is evaluated (the reference's fill, then add), so
+ * a = b = -0 stores +0.  state_prev may be null (no shortcut) or state_next
+ * itself (inference, where the step writes the slice it reads).
+ * tns_hip_rnn_delta_backward:
+ *   d = clamp1(delta[k]) * grad(out[k], act);     d -> delta[k]
+ *   delta2[k] = clamp1(d) * grad(out2[k], act2)   (delta2 not null)
+ * clamp1(v) = v < -1 ? -1 : v > 1 ? 1 : v (a NaN stays): the clamp(delta, 1)
+ * + DeriveArray that open a sub-layer's backward, on one slice; with delta2
+ * also the copy into the input sub-layer's delta and that sub-layer's clamp +
+ * DeriveArray (valid when the self sub-layer is not batch-normalized).
+ * TNS_ERR_ARG, before any launch and with every output untouched: N < 0,
+ * H < 1, a null operand with N > 0 (the biases, state_prev and delta2 / out2
+ * without delta2 excepted), an output (in_slice, self_slice, state_next;
+ * delta, delta2) overlapping any other operand — state_prev == state_next is
+ * one operand.  TNS_ERR_UNSUPPORTED: an activation ActivateArray rejects.
+ * Inputs may overlap one another.  N == 0 does nothing. */
+int tns_hip_rnn_state_forward(tns_ctx* ctx, int64_t N, int64_t H, float* in_slice,
+                              const float* in_bias, int32_t in_act, float* self_slice,
+                              const float* self_bias, int32_t self_act,
+                              const float* state_prev, float* state_next);
+int tns_hip_rnn_delta_backward(tns_ctx* ctx, int64_t N, float* delta, const float* out,
+                               int32_t act, float* delta2, const float* out2, int32_t act2);
+
 /* ---- batch norm / softmax (TNNCuda twins, nncuda.pas:1056-1510; CPU
  * semantics ntensors.pas:7687-7830, 8693-8951, 9102-9177,
  * nsoftmaxlayer.pas:83-137).  Data is [groups][channels][blockSize]. ---- */

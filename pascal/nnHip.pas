@@ -221,6 +221,15 @@ function tns_hip_lstm_gates_backward(ctx: PTnsCtx; N: int64; wf, wi, wg, wo, uf,
   cell_i, cprev, delta_i, dc, dwf, dwi, dwg, dwo, duf, dui, dug, duo: THipMem): longint;
   cdecl; external libtns;
 
+{ the elementwise stage of one RNN time step (rnn.hip): in_slice / self_slice the
+  step's slices of the input / self sub-layers' outputs, in place; a bias,
+  state_prev and delta2 may be nil; state_prev may be state_next }
+function tns_hip_rnn_state_forward(ctx: PTnsCtx; N, H: int64; in_slice, in_bias: THipMem;
+  in_act: longint; self_slice, self_bias: THipMem; self_act: longint; state_prev,
+  state_next: THipMem): longint; cdecl; external libtns;
+function tns_hip_rnn_delta_backward(ctx: PTnsCtx; N: int64; delta, output: THipMem; act: longint;
+  delta2, output2: THipMem; act2: longint): longint; cdecl; external libtns;
+
 { batch norm / softmax }
 function tns_hip_means_and_vars(ctx: PTnsCtx; srcSize, dstSize, groups: int64; src: THipMem;
   offset: int64; means, vars: THipMem): longint; cdecl; external libtns;
@@ -390,6 +399,10 @@ type
       (INTEGRATION.md); the offsets are in elements, as everywhere }
     procedure lstmGatesForward(const N: SizeInt; const wf, wi, wg, wo, uf, ui, ug, uo: TCUMem; const offset: SizeInt; const c_state, h_state, cell, output: TCUMem);
     procedure lstmGatesBackward(const N: SizeInt; const wf, wi, wg, wo, uf, ui, ug, uo: TCUMem; const offset: SizeInt; const cell, cprev: TCUMem; const cprevOffset: SizeInt; const delta, dc, dwf, dwi, dwg, dwo, duf, dui, dug, duo: TCUMem);
+    { the elementwise calls of one step of TRNNLayer.forward / backward fused
+      (INTEGRATION.md); a bias, statePrev and delta2 may be nil }
+    procedure rnnStateForward(const N, H: SizeInt; const inOut: TCUMem; const inOffset: SizeInt; const inBias: TCUMem; const inAct: longint; const selfOut: TCUMem; const selfOffset: SizeInt; const selfBias: TCUMem; const selfAct: longint; const statePrev: TCUMem; const prevOffset: SizeInt; const stateNext: TCUMem; const nextOffset: SizeInt);
+    procedure rnnDeltaBackward(const N: SizeInt; const delta: TCUMem; const deltaOffset: SizeInt; const output: TCUMem; const outputOffset: SizeInt; const act: longint; const delta2: TCUMem; const delta2Offset: SizeInt; const output2: TCUMem; const output2Offset: SizeInt; const act2: longint);
 
     property ctx: PTnsCtx read FCtx;
   end;
@@ -753,6 +766,29 @@ begin
   check(tns_hip_lstm_gates_backward(FCtx, N, at(wf), at(wi), at(wg), at(wo), at(uf), at(ui),
     at(ug), at(uo), at(cell), THipMem(cprev) + cprevOffset, at(delta), THipMem(dc), at(dwf),
     at(dwi), at(dwg), at(dwo), at(duf), at(dui), at(dug), at(duo)))
+end;
+
+procedure TNNHip<T>.rnnStateForward(const N, H: SizeInt; const inOut: TCUMem; const inOffset: SizeInt; const inBias: TCUMem; const inAct: longint; const selfOut: TCUMem; const selfOffset: SizeInt; const selfBias: TCUMem; const selfAct: longint; const statePrev: TCUMem; const prevOffset: SizeInt; const stateNext: TCUMem; const nextOffset: SizeInt);
+var prev: THipMem;
+begin
+  prev := nil;
+  if statePrev <> nil then prev := THipMem(statePrev) + prevOffset;
+  check(tns_hip_rnn_state_forward(FCtx, N, H, THipMem(inOut) + inOffset, THipMem(inBias), inAct,
+    THipMem(selfOut) + selfOffset, THipMem(selfBias), selfAct, prev,
+    THipMem(stateNext) + nextOffset))
+end;
+
+procedure TNNHip<T>.rnnDeltaBackward(const N: SizeInt; const delta: TCUMem; const deltaOffset: SizeInt; const output: TCUMem; const outputOffset: SizeInt; const act: longint; const delta2: TCUMem; const delta2Offset: SizeInt; const output2: TCUMem; const output2Offset: SizeInt; const act2: longint);
+var d2, o2: THipMem;
+begin
+  d2 := nil;
+  o2 := nil;
+  if delta2 <> nil then begin
+    d2 := THipMem(delta2) + delta2Offset;
+    o2 := THipMem(output2) + output2Offset
+  end;
+  check(tns_hip_rnn_delta_backward(FCtx, N, THipMem(delta) + deltaOffset,
+    THipMem(output) + outputOffset, act, d2, o2, act2))
 end;
 
 procedure TNNHip<T>.clamp(const N: SizeInt; const alpha: T; const src, dst: TCUMem; const stride: SizeInt; offset: SizeInt);

@@ -211,6 +211,11 @@ PROTOTYPES.update({
     # the LSTM gate stage: 8 pre-activation slices, then the state / slices
     "tns_hip_lstm_gates_forward": (C.c_int, [vp, i64] + [fptr] * 12),
     "tns_hip_lstm_gates_backward": (C.c_int, [vp, i64] + [fptr] * 20),
+    # the RNN step stage: N, H, (slice, bias, act) x 2, state_prev, state_next;
+    # N, (delta, out, act) x 2
+    "tns_hip_rnn_state_forward": (C.c_int, [vp, i64, i64, fptr, fptr, i32, fptr, fptr, i32, fptr,
+                                            fptr]),
+    "tns_hip_rnn_delta_backward": (C.c_int, [vp, i64, fptr, fptr, i32, fptr, fptr, i32]),
     "tns_hip_means_and_vars": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),
     "tns_hip_means": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr]),
     "tns_hip_variances": (C.c_int, [vp, i64, i64, i64, fptr, i64, fptr, fptr]),

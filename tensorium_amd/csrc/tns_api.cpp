@@ -1544,6 +1544,81 @@ int tns_hip_lstm_gates_backward(tns_ctx* c, int64_t N, const float* wf, const fl
                     "lstmGatesBackward");
 }
 
+namespace {
+
+// the RNN step entries: operands as (pointer, floats); the first n_out are
+// written.  No output may meet any other operand (an in / out operand is one
+// operand; null operands meet nothing); inputs may meet one another
+struct RnnOp {
+  const float* p;
+  int64_t n;
+};
+int rnn_overlap(const char* what, std::initializer_list<RnnOp> ops, size_t n_out) {
+  auto meet = [](const RnnOp& a, const RnnOp& b) {
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    return a.p && b.p && x < y + (uintptr_t)b.n * sizeof(float) &&
+           y < x + (uintptr_t)a.n * sizeof(float);
+  };
+  const RnnOp* o = ops.begin();
+  for (size_t a = 0; a < n_out; ++a)
+    for (size_t b = 0; b < ops.size(); ++b)
+      if (b != a && (b > a || b >= n_out) && meet(o[a], o[b]))
+        return set_error(TNS_ERR_ARG, "%s: an output overlaps another operand", what);
+  return TNS_OK;
+}
+
+}  // namespace
+
+int tns_hip_rnn_state_forward(tns_ctx* c, int64_t N, int64_t H, float* in_slice,
+                              const float* in_bias, int32_t in_act, float* self_slice,
+                              const float* self_bias, int32_t self_act, const float* state_prev,
+                              float* state_next) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (N < 0 || H < 1)
+    return set_error(TNS_ERR_ARG, "rnnStateForward: N = %lld, H = %lld", (long long)N,
+                     (long long)H);
+  if (!act_supported(in_act) || !act_supported(self_act))
+    return set_error(TNS_ERR_UNSUPPORTED, "rnnStateForward: activation %d / %d not implemented",
+                     in_act, self_act);
+  if (N == 0) return TNS_OK;
+  if (!in_slice || !self_slice || !state_next)
+    return set_error(TNS_ERR_ARG, "rnnStateForward: null operand");
+  // state_prev == state_next is the in-place call (inference, j = i)
+  const float* prev = state_prev == state_next ? nullptr : state_prev;
+  if (int r = rnn_overlap("rnnStateForward",
+                          {{in_slice, N}, {self_slice, N}, {state_next, N}, {prev, N},
+                           {in_bias, H}, {self_bias, H}},
+                          3))
+    return r;
+  if (int r = check_ops(c, {span(in_slice, N), span(self_slice, N), span(state_next, N)},
+                        {span(state_prev, N), span(in_bias, H), span(self_bias, H)}))
+    return r;
+  return hip_status(launch_rnn_state_forward(N, H, in_slice, in_bias, in_act, self_slice,
+                                             self_bias, self_act, state_prev, state_next,
+                                             c->stream),
+                    "rnnStateForward");
+}
+
+int tns_hip_rnn_delta_backward(tns_ctx* c, int64_t N, float* delta, const float* out, int32_t act,
+                               float* delta2, const float* out2, int32_t act2) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (N < 0) return set_error(TNS_ERR_ARG, "rnnDeltaBackward: N = %lld", (long long)N);
+  if (!act_supported(act) || (delta2 && !act_supported(act2)))
+    return set_error(TNS_ERR_UNSUPPORTED, "rnnDeltaBackward: derivative %d / %d not implemented",
+                     act, act2);
+  if (N == 0) return TNS_OK;
+  if (!delta || !out || (delta2 && !out2))
+    return set_error(TNS_ERR_ARG, "rnnDeltaBackward: null operand");
+  if (int r = rnn_overlap("rnnDeltaBackward",
+                          {{delta, N}, {delta2, N}, {out, N}, {delta2 ? out2 : nullptr, N}}, 2))
+    return r;
+  if (int r = check_ops(c, {span(delta, N), span(delta2, N)},
+                        {span(out, N), span(delta2 ? out2 : nullptr, N)}))
+    return r;
+  return hip_status(launch_rnn_delta_backward(N, delta, out, act, delta2, out2, act2, c->stream),
+                    "rnnDeltaBackward");
+}
+
 int tns_hip_clamp(tns_ctx* c, int64_t N, float alpha, const float* src, float* dst,
                   int64_t stride, int64_t offset) {
   if (int r = check_ops(c, {span(dst ? dst + offset : nullptr, N, stride)},

@@ -334,6 +334,15 @@ hipError_t launch_lstm_gates_backward(int64_t n, const float* const w[4], const 
                                       const float* cell_i, const float* cprev,
                                       const float* delta_i, float* dc, float* const dw[4],
                                       float* const du[4], hipStream_t s);
+// rnn.hip: the elementwise stage of one RNN time step (a bias, state_prev and
+// delta2 may be null; in_slice, self_slice and delta are in / out; state_prev
+// may be state_next)
+hipError_t launch_rnn_state_forward(int64_t n, int64_t H, float* in_slice, const float* in_bias,
+                                    int in_act, float* self_slice, const float* self_bias,
+                                    int self_act, const float* state_prev, float* state_next,
+                                    hipStream_t s);
+hipError_t launch_rnn_delta_backward(int64_t n, float* delta, const float* out, int act,
+                                     float* delta2, const float* out2, int act2, hipStream_t s);
 // TNNCuda addvv/subvv/mulvv/fmavv (op 0..3), fmavss, inverseSqrt
 hipError_t launch_vv(int op, int64_t n, const float* a, int64_t inca, const float* b, int64_t incb,
                      const float* c, int64_t incc, float* d, int64_t incd, hipStream_t s);

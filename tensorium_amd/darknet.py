@@ -5,7 +5,7 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
 * ``parse_cfg(text)``: darknet INI sections (nparser.pas:154-246 reads the
   same format through TCFGList): ``[type]`` lines, ``key=value`` options,
   ``#`` / ``;`` comments.
-* ``Network(sections, batch)``: shapes of every layer exactly as the
+* ``Network(sections, batch, rnn=False)``: shapes of every layer exactly as the
   reference's parser derives them (nparser.pas:782-930): convolutional
   (``pad=1`` => padding = size div 2, nparser.pas:186-189; out = (in + 2p - k)
   div stride + 1, nConvolutionLayer.pas:92-100), shortcut (TAddLayer,
@@ -16,8 +16,9 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   classifier kinds connected / dropout / softmax / cost / logistic
   (parseConnected 146-152, parseDropOut 301-331, parseLogistic 714-720,
   parseSoftmax 722-738, parseCost 740-755), and lstm (TLSTMLayer,
-  nlstmlayer.pas; parseLSTM 501-504) with ``[net]``'s ``time_steps`` and
-  ``inputs`` (nparser.pas:813-818, 962-972).
+  nlstmlayer.pas; parseLSTM 501-504) and rnn (TRNNLayer, nrnnlayer.pas;
+  parseRNN 489-499) with ``[net]``'s ``time_steps`` and ``inputs``
+  (nparser.pas:813-818, 962-972).
 * ``load_weights`` / ``write_weights``: the darknet .weights layout read by
   TDarknetParser.loadWeights (nparser.pas:1275-1330): int32 major, minor,
   revision, then ``seen`` as uint64 when major*10+minor >= 2 (else uint32),
@@ -27,7 +28,8 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   biases[O], weights[O*I], then (scales, rolling_mean, rolling_variance)[O]
   when batch-normalized (loadConnectedWeights, nparser.pas:1102-1128); per
   lstm layer eight connected blocks in the order wf wi wg wo uf ui ug uo
-  (nparser.pas:1347-1357).
+  (nparser.pas:1347-1357); per rnn layer three connected blocks in the order
+  input, self, output (nparser.pas:1326-1331).
 * ``fuse_batchnorm``: TBaseConvolutionalLayer.fuseBatchNorm
   (nConvolutionLayer.pas:102-126) in float32: p = scale / sqrt(max(var,
   1e-6)); bias -= mean * p; W *= p.
@@ -83,7 +85,7 @@ class Layer:
     index: int
     kind: str            # convolutional | shortcut | route | upsample | yolo |
                          # maxpool | local_avgpool | connected | dropout |
-                         # softmax | cost | logistic | lstm
+                         # softmax | cost | logistic | lstm | rnn
     c: int               # input channels / height / width
     h: int
     w: int
@@ -106,8 +108,12 @@ class Layer:
     groups: int = 1            # softmax
     temperature: float = 1.0
     noloss: bool = False
-    steps: int = 1             # lstm: time steps; its batch is Network.batch div steps
-    gate: str = ""             # a connected block of an lstm layer: wf .. uo
+    steps: int = 1             # lstm / rnn: time steps; its batch is Network.batch div steps
+    gate: str = ""             # a connected block of an lstm layer: wf .. uo; of an rnn
+                               # layer: input | self | output
+    hidden: int = 0            # rnn: the state's width (filters is its output's)
+    self_activation: int = ACT["LINEAR"]  # rnn: the self sub-layer's (logistic=1: LOGISTIC)
+    shortcut: bool = False     # rnn: TRNNLayer.isShortcut, a public field no cfg key sets
 
     def __post_init__(self):
         self.stride_x = self.stride_x or self.stride
@@ -138,15 +144,24 @@ def _flag(sec: Section, key: str) -> bool:
 # kinds that read params.c / h / w, which the reference leaves stale after a
 # layer that is no TBaseImageLayer (nparser.pas:913-919)
 LSTM_GATES = ("wf", "wi", "wg", "wo", "uf", "ui", "ug", "uo")  # file / update order
+RNN_SUBS = ("input", "self", "output")  # file / update order
+# the activations the backend implements (act_supported, elementwise.hip)
+ACT_SUPPORTED = tuple(ACT[k] for k in ("LOGISTIC", "RELU", "LINEAR", "TANH", "REVLEAKY", "LEAKY",
+                                       "HARDTAN"))
 
 _IMAGE_KINDS = ("convolutional", "conv", "shortcut", "route", "concat", "upsample", "yolo",
                 "maxpool", "max", "local_avgpool")
 
 
 class Network:
-    """Layer plan with shapes (nparser.pas:782-930)."""
+    """Layer plan with shapes (nparser.pas:782-930).
 
-    def __init__(self, sections: list[Section], batch: int | None = None):
+    ``rnn=True`` plans ``[rnn]`` sections.  Without it they are refused as
+    before the layer was built, with the other recurrent kinds: callers (and
+    tests/test_lstm.py) that rely on a plan holding only what they know keep
+    that, and a caller that drives rnn layers says so."""
+
+    def __init__(self, sections: list[Section], batch: int | None = None, rnn: bool = False):
         net = sections[0]
         # Neural.batch := mini_batch * timeSteps (nparser.pas:962-972); a
         # batch argument replaces the whole product (ABatch, 802-803)
@@ -168,9 +183,10 @@ class Network:
         for sec in sections[1:]:
             i = len(self.layers)
             if flat and sec.kind in _IMAGE_KINDS:
-                raise ValueError(f"[{sec.kind}] layer {i} after a [connected] or [lstm] layer, or "
-                                 "in a network of inputs= rows: the reference plans it on the "
-                                 "image shape of an earlier layer (nparser.pas:913-919); refused")
+                raise ValueError(f"[{sec.kind}] layer {i} after a [connected], [lstm] or [rnn] "
+                                 "layer, or in a network of inputs= rows: the reference plans it "
+                                 "on the image shape of an earlier layer (nparser.pas:913-919); "
+                                 "refused")
             if sec.kind in ("convolutional", "conv"):
                 size = sec.int("size", 1)
                 stride = sec.int("stride", 1)
@@ -243,6 +259,30 @@ class Network:
                 lay = Layer(i, "lstm", c, h, w, o, 1, 1, filters=o, bn=_flag(sec, "batch_normalize"),
                             steps=self.time_steps)
                 flat = True
+            elif sec.kind == "rnn" and rnn:
+                # parseRNN (nparser.pas:489-499); the layer's own batch is
+                # Network.batch div time_steps (nrnnlayer.pas:49), a remainder
+                # refused as for [lstm].  The self sub-layer's activation is
+                # the layer's, LOGISTIC with logistic=1, LOGGY with logistic=2
+                # (nrnnlayer.pas:66)
+                o, hid = sec.int("output", 1), sec.int("hidden", 1)
+                if o < 1 or hid < 1 or c * h * w < 1:
+                    raise ValueError(f"[rnn] layer {i}: {c * h * w} inputs, hidden={hid}, "
+                                     f"output={o}")
+                if self.batch % self.time_steps:
+                    raise ValueError(f"[rnn] layer {i}: batch {self.batch} is no multiple of "
+                                     f"time_steps {self.time_steps}")
+                name = sec.get("activation", "logistic").strip().upper()
+                log = sec.int("logistic", 0)
+                if log == 2:
+                    raise ValueError(f"[rnn] layer {i}: logistic=2 selects the LOGGY activation "
+                                     "for the self sub-layer, which is not built")
+                if ACT.get(name) not in ACT_SUPPORTED:
+                    raise ValueError(f"[rnn] layer {i}: activation={name.lower()} is not built")
+                lay = Layer(i, "rnn", c, h, w, o, 1, 1, filters=o, activation=ACT[name],
+                            bn=_flag(sec, "batch_normalize"), steps=self.time_steps, hidden=hid,
+                            self_activation=ACT["LOGISTIC"] if log == 1 else ACT[name])
+                flat = True
             elif sec.kind == "dropout":
                 # probability is a single; scale := 1 / (1.0 - probability) in
                 # double, stored as single (ndropoutlayer.pas:65)
@@ -273,6 +313,9 @@ class Network:
                             scale=float(np.float32(sec.get("scale", 1))))
             elif sec.kind == "logistic":
                 lay = Layer(i, "logistic", c, h, w, c, h, w, activation=ACT["LOGISTIC"])
+            elif sec.kind == "rnn":
+                raise ValueError("[Parser][rnn] layer is not yet implemented! (in the default "
+                                 "plan: Network(sections, batch, rnn=True) plans it)")
             else:
                 raise ValueError(f"[Parser][{sec.kind}] layer is not yet implemented!")
             self.layers.append(lay)
@@ -286,7 +329,9 @@ class Network:
         nparser.pas:1309-1357): the convolutional and connected layers, and
         for an lstm layer its eight connected sub-layers wf wi wg wo ([O][O])
         uf ui ug uo ([O][inputs]) as connected blocks carrying the layer's
-        index and their name in ``gate``."""
+        index and their name in ``gate``; for an rnn layer its three connected
+        sub-layers input ([hidden][inputs]), self ([hidden][hidden]) and
+        output ([O][hidden]) the same way, each with its own activation."""
         out = []
         for l in self.layers:
             if l.kind in ("convolutional", "connected"):
@@ -296,10 +341,19 @@ class Network:
                     n = l.filters if g[0] == "w" else l.in_size
                     out.append(Layer(l.index, "connected", n, 1, 1, l.filters, 1, 1,
                                      filters=l.filters, bn=l.bn, gate=g))
+            elif l.kind == "rnn":
+                for g, n, o, act in (("input", l.in_size, l.hidden, l.activation),
+                                     ("self", l.hidden, l.hidden, l.self_activation),
+                                     ("output", l.hidden, l.filters, l.activation)):
+                    out.append(Layer(l.index, "connected", n, 1, 1, o, 1, 1, filters=o,
+                                     activation=act, bn=l.bn, gate=g))
         return out
 
     def lstms(self) -> list[Layer]:
         return [l for l in self.layers if l.kind == "lstm"]
+
+    def rnns(self) -> list[Layer]:
+        return [l for l in self.layers if l.kind == "rnn"]
 
 
 def yolov3_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
@@ -446,6 +500,25 @@ def lstm_cfg(batch: int = 1, time_steps: int = 1, inputs: int = 256, hidden: int
     out = [f"[net]\nbatch={batch}\nsubdivisions=1\ninputs={inputs}\ntime_steps={time_steps}\n"]
     for _ in range(layers):
         out.append(f"[lstm]\n{'batch_normalize=1' + chr(10) if bn else ''}output={hidden}\n")
+    out += [f"[connected]\noutput={inputs}\nactivation=linear\n", "[softmax]\n"]
+    if cost:
+        out.append("[cost]\ntype=sse\n")
+    return "\n".join(out)
+
+
+def rnn_cfg(batch: int = 1, time_steps: int = 1, inputs: int = 256, hidden: int = 1024,
+            layers: int = 3, bn: bool = True, activation: str = "leaky", cost: bool = True) -> str:
+    """The public char-RNN structure: ``layers`` stacked [rnn] of ``hidden``
+    state and outputs over rows of ``inputs`` floats, a linear [connected]
+    back to ``inputs``, [softmax], optionally [cost] type=sse.  The
+    reference's sample loads its cfg from outside its tree
+    (shakespeare_infer_rnn.pas), so this is the common structure, not a file
+    that can be compared against.  Plan it with ``Network(parse_cfg(...),
+    rnn=True)``."""
+    out = [f"[net]\nbatch={batch}\nsubdivisions=1\ninputs={inputs}\ntime_steps={time_steps}\n"]
+    for _ in range(layers):
+        out.append(f"[rnn]\n{'batch_normalize=1' + chr(10) if bn else ''}output={hidden}\n"
+                   f"hidden={hidden}\nactivation={activation}\n")
     out += [f"[connected]\noutput={inputs}\nactivation=linear\n", "[softmax]\n"]
     if cost:
         out.append("[cost]\ntype=sse\n")
@@ -638,13 +711,24 @@ class _LstmLayers:
                 L[k].zero_()
 
     # -- one sub-layer, one step: TConnectedLayer.forwardGPU / backwardGPU ----
-    def _sub_bn_forward(self, l, L, st, step, training):
+    @staticmethod
+    def _sub_dims(l, L, st):
+        """A sub-layer's outputs and one step's slice of them: the layer's for
+        an lstm gate; an rnn sub-layer carries its own (``O``, and ``act``)."""
+        O = st.get("O", l.filters)
+        return O, L["S"] * O
+
+    def _sub_bn_forward(self, l, L, st, step, training, activate=True):
         """What follows the product (nconnectedlayer.pas:654-733) on step's
-        slice; one mean / variance pair per sub-layer, overwritten each step."""
-        hip, S, O, n = self.hip, L["S"], l.filters, L["n"]
+        slice; one mean / variance pair per sub-layer, overwritten each step.
+        activate=False: without the bias add (no batch norm) and the
+        activation, which rnnStateForward makes."""
+        hip, S = self.hip, L["S"]
+        O, n = self._sub_dims(l, L, st)
         out, off = st["out"], step * n
         if not l.bn:
-            hip.forwardBias(n, out, off, O, st["b"], 1, S)
+            if activate:
+                hip.forwardBias(n, out, off, O, st["b"], 1, S)
         else:
             if training:
                 mom = np.float32(0.05)  # bnMomentum (nconnectedlayer.pas:67)
@@ -661,22 +745,27 @@ class _LstmLayers:
             else:
                 hip.normalize(O, n, S, st["rm"], 1, st["rv"], 1, out, off)
             hip.forwardScaleAdd(n, out, off, O, st["scales"], st["b"], 1, S)
-        hip.ActivateArray(n, out, off, ACT["LINEAR"])
+        if activate:
+            hip.ActivateArray(n, out, off, st.get("act", ACT["LINEAR"]))
 
     def _sub_forward(self, l, L, st, step, inp, in_step, training):
-        S, O, I, n = L["S"], l.filters, st["I"], L["n"]
+        S, I = L["S"], st["I"]
+        O, n = self._sub_dims(l, L, st)
         self.hip.gemm(False, True, S, O, I, 1.0, inp, in_step * S * I, I, st["w"], 0, I, 0.0,
                       st["out"], step * n, O)
         self._sub_bn_forward(l, L, st, step, training)
 
     def _sub_bn_backward(self, l, L, st, step, clamp):
         """Up to the two products (nconnectedlayer.pas:771-821).  clamp=False:
-        lstmGatesBackward stored the slice clamped already."""
-        hip, S, T, O, n = self.hip, L["S"], L["T"], l.filters, L["n"]
+        lstmGatesBackward stored the slice clamped already (rnnDeltaBackward:
+        clamped and derived)."""
+        hip, S, T = self.hip, L["S"], L["T"]
+        O, n = self._sub_dims(l, L, st)
         d, off = st["delta"], step * n
         if clamp:
             hip.clamp(T * n, 1.0, d, d)
-            hip.DeriveArray(n, st["out"], off, ACT["LINEAR"], d)
+            # (the slice's own delta: with an lstm gate's LINEAR it multiplies by one)
+            hip.DeriveArray(n, st["out"], off, st.get("act", ACT["LINEAR"]), self._at(d, off))
         hip.backwardBias(O, st["bu"], n, d, off, 1, S)
         if l.bn:
             hip.addDots(n, O, S, st["xn"], d, off, st["su"])
@@ -685,9 +774,10 @@ class _LstmLayers:
                                   st["vd"])
             hip.normalizeDelta(n, O, S, d, st["x"], off, st["mean"], st["var"], st["md"], st["vd"])
 
-    def _sub_backward(self, l, L, st, step, inp, in_step, sd, sd_step):
-        hip, S, O, I, n = self.hip, L["S"], l.filters, st["I"], L["n"]
-        self._sub_bn_backward(l, L, st, step, True)
+    def _sub_backward(self, l, L, st, step, inp, in_step, sd, sd_step, clamp=True):
+        hip, S, I = self.hip, L["S"], st["I"]
+        O, n = self._sub_dims(l, L, st)
+        self._sub_bn_backward(l, L, st, step, clamp)
         d, off = st["delta"], step * n
         hip.gemm(True, False, O, I, S, 1.0, d, off, O, inp, in_step * S * I, I, 1.0, st["wu"], 0, I)
         if sd is not None:
@@ -834,7 +924,175 @@ class _LstmLayers:
                                self.net.batch, decay, momentum, st.get("scales"), st.get("su"))
 
 
-class HipDarknet(_LstmLayers):
+class _RnnLayers:
+    """The rnn layers of a driver (TRNNLayer.forward / backward / update, the
+    CPU path, nrnnlayer.pas:148-257, 345-400 — the reference's device path
+    disagrees with it), beside ``_LstmLayers``, whose sub-layer
+    helpers it uses.  Rows are [step][stream]; n = streams * hidden floats
+    make one hidden slice, m = streams * outputs one output slice.
+
+    State per layer: ``state`` ((steps + 1) * n, zero at construction; a
+    training forward zeroes slice 0, an inference forward nothing) and the
+    three connected sub-layers input, self, output with what ``_fc_forward`` /
+    ``_fc_backward`` keep, outputs and deltas steps * n (steps * m) long.  The
+    output sub-layer's output and delta ARE the layer's.
+
+    ``rnn_fused=False`` is the reference's call sequence, call for call
+    through the existing TNNHip methods, the whole-delta clamp of every
+    sub-layer backward included.  ``rnn_fused=True`` is the product path: one
+    ``rnnStateForward`` per step, ``rnnDeltaBackward`` for the clamp + derive
+    (+ copy + clamp + derive), and products regrouped only where every output
+    element keeps its operands and its order of additions (the RNN
+    section)."""
+
+    def _rnn_init(self, blocks, training):
+        torch, dev = self.torch, "cuda"
+        z = lambda n: torch.zeros(n, device=dev)  # noqa: E731
+        self.rnn = {}
+        by_layer = {}
+        for l, p in blocks:
+            by_layer.setdefault(l.index, {})[l.gate] = (l, p)
+        for l in self.net.rnns():
+            T = l.steps
+            S = self.net.batch // T
+            L = {"S": S, "T": T, "n": S * l.hidden, "m": S * l.filters,
+                 "state": z((T + 1) * S * l.hidden), "sub": {}}
+            for g in RNN_SUBS:
+                b, p = by_layer[l.index][g]
+                O, K = b.filters, b.in_size
+                own = g == "output"  # the layer's own buffers
+                st = {"I": K, "O": O, "act": b.activation, "w": self._t(p.weights).reshape(-1),
+                      "b": self._t(p.biases),
+                      "out": self.out[l.index] if own else z(T * S * O)}
+                if l.bn:
+                    st.update(scales=self._t(p.scales), rm=self._t(p.rolling_mean),
+                              rv=self._t(p.rolling_var))
+                if training:
+                    st.update(wu=z(O * K), bu=z(O),
+                              delta=self.delta[l.index] if own else z(T * S * O))
+                    if l.bn:
+                        st.update(mean=z(O), var=z(O), x=z(T * S * O), xn=z(T * S * O), su=z(O),
+                                  md=z(O), vd=z(O))
+                L["sub"][g] = st
+            self.rnn[l.index] = L
+
+    def reset_state(self):
+        """Zero every rnn layer's whole ``state`` (no inference pass does: the
+        reference carries it from call to call), and the lstm layers' state."""
+        for L in self.rnn.values():
+            L["state"].zero_()
+        super().reset_state()
+
+    # -- forward ---------------------------------------------------------------
+    def _rnn_forward(self, l, inp, training):
+        hip, L, at = self.hip, self.rnn[l.index], self._at
+        S, T, n, m, H, O, I = L["S"], L["T"], L["n"], L["m"], l.hidden, l.filters, l.in_size
+        si, ss, so = (L["sub"][g] for g in RNN_SUBS)
+        state = L["state"]
+        inp = inp.reshape(-1)
+        if training:  # nrnnlayer.pas:241-246: delta.multiply(0), state.FillExt(0, 0, n)
+            hip.scale(T * m, 0.0, so["delta"], 1)
+            hip.scale(T * n, 0.0, ss["delta"], 1)
+            hip.scale(T * n, 0.0, si["delta"], 1)
+            hip.fill(n, state, 0, 0.0, 1)
+        j0 = 1 if training else 0  # step i writes state[i + j0] (rnnStepForward's j)
+        if not self.rnn_fused:
+            for i in range(T):
+                j = i + j0
+                self._sub_forward(l, L, si, i, inp, i, training)
+                self._sub_forward(l, L, ss, i, state, i, training)
+                if not l.shortcut:
+                    hip.fill(n, state, j * n, 0.0, 1)
+                elif j != i:  # (j = i: the slice onto itself)
+                    hip.copy(n, state, i * n, 1, state, j * n, 1)
+                hip.addvv(n, state, j * n, 1, si["out"], i * n, 1, state, j * n, 1)
+                hip.addvv(n, state, j * n, 1, ss["out"], i * n, 1, state, j * n, 1)
+                self._sub_forward(l, L, so, i, state, j, training)
+            return
+        # the input sub-layer's products of every step at once: an NT product's
+        # element is one sdot of an input row and a weight row
+        hip.gemm(False, True, T * S, H, I, 1.0, inp, 0, I, si["w"], 0, I, 0.0, si["out"], 0, H)
+        if l.bn and not training:  # by the rolling statistics: per element, any grouping
+            hip.normalize(H, T * n, T * S, si["rm"], 1, si["rv"], 1, si["out"], 0)
+            hip.forwardScaleAdd(T * n, si["out"], 0, H, si["scales"], si["b"], 1, T * S)
+        for i in range(T):
+            off = i * n
+            hip.gemm(False, True, S, H, H, 1.0, state, off, H, ss["w"], 0, H, 0.0, ss["out"], off,
+                     H)
+            if l.bn:  # training: the statistics are per step
+                if training:
+                    self._sub_bn_forward(l, L, si, i, True, activate=False)
+                self._sub_bn_forward(l, L, ss, i, training, activate=False)
+            hip.rnnStateForward(n, H, at(si["out"], off), None if l.bn else si["b"], si["act"],
+                                at(ss["out"], off), None if l.bn else ss["b"], ss["act"],
+                                at(state, off) if l.shortcut else None, at(state, off + j0 * n))
+        # the output sub-layer after the loop: step i reads state[i + j0], which
+        # step i alone writes and no later step changes (in inference the steps
+        # of one call do not chain: step i + 1 reads state[i + 1], not this one)
+        hip.gemm(False, True, T * S, O, H, 1.0, state, j0 * n, H, so["w"], 0, H, 0.0, so["out"], 0,
+                 O)
+        if not l.bn:
+            hip.forwardBias(T * m, so["out"], 0, O, so["b"], 1, T * S)
+        elif training:
+            for i in range(T):
+                self._sub_bn_forward(l, L, so, i, True, activate=False)
+        else:
+            hip.normalize(O, T * m, T * S, so["rm"], 1, so["rv"], 1, so["out"], 0)
+            hip.forwardScaleAdd(T * m, so["out"], 0, O, so["scales"], so["b"], 1, T * S)
+        hip.ActivateArray(T * m, so["out"], 0, so["act"])
+
+    # -- backward ----------------------------------------------------------------
+    def _rnn_backward(self, l, inp, sd):
+        hip, L, at = self.hip, self.rnn[l.index], self._at
+        S, T, n, m, H, I = L["S"], L["T"], L["n"], L["m"], l.hidden, l.in_size
+        si, ss, so = (L["sub"][g] for g in RNN_SUBS)
+        state = L["state"]
+        inp = inp.reshape(-1)
+        fused = self.rnn_fused
+        for i in range(T - 1, -1, -1):
+            off, offm = i * n, i * m
+            # one add over the forward's value (the shortcut term dropped, as
+            # the reference drops it); state[i] below is still the forward's
+            hip.addvv(n, si["out"], off, 1, ss["out"], off, 1, state, off + n, 1)
+            if fused:
+                hip.rnnDeltaBackward(m, at(so["delta"], offm), at(so["out"], offm), so["act"])
+            self._sub_backward(l, L, so, i, state, i + 1, ss["delta"], i, clamp=not fused)
+            if fused:  # without batch norm the slice is final here: the input
+                # sub-layer's copy, clamp and derive ride along
+                chain = not l.bn
+                hip.rnnDeltaBackward(n, at(ss["delta"], off), at(ss["out"], off), ss["act"],
+                                     at(si["delta"], off) if chain else None,
+                                     at(si["out"], off) if chain else None, si["act"])
+            self._sub_backward(l, L, ss, i, state, i, ss["delta"] if i else None, i - 1,
+                               clamp=not fused)
+            if not fused or l.bn:
+                hip.copy(n, ss["delta"], off, 1, si["delta"], off, 1)
+            if fused and l.bn:
+                hip.rnnDeltaBackward(n, at(si["delta"], off), at(si["out"], off), si["act"])
+            if i and l.shortcut:
+                hip.addvv(n, ss["delta"], off - n, 1, ss["delta"], off, 1, ss["delta"], off - n, 1)
+            self._sub_backward(l, L, si, i, inp, i, None if fused else sd, i, clamp=not fused)
+        if not fused:
+            return
+        if sd is not None:  # slice i of the layer below's delta takes step i's product alone
+            hip.gemm(False, False, T * S, I, H, 1.0, si["delta"], 0, H, si["w"], 0, I, 1.0, sd, 0,
+                     I)
+        if l.bn and T > 1:
+            # the reference clamps the whole delta at every step: a slice that
+            # normalizeDelta pushed outside [-1, 1] is clamped by the next step
+            # (and no further: clamping is idempotent).  Nothing reads slice i
+            # after step i, so one clamp of slices 1 .. T-1 leaves the layer's
+            # delta as the reference does; slice 0 is processed last
+            hip.clamp((T - 1) * m, 1.0, so["delta"], so["delta"], 1, m)
+
+    def _rnn_update(self, l, learning_rate, momentum, decay):
+        for g in RNN_SUBS:  # TRNNLayer.update's order (nrnnlayer.pas:393-395)
+            st = self.rnn[l.index]["sub"][g]
+            self.hip.sgdUpdate(st["w"], st["wu"], st["b"], st["bu"], learning_rate,
+                               self.net.batch, decay, momentum, st.get("scales"), st.get("su"))
+
+
+class HipDarknet(_RnnLayers, _LstmLayers):
     """TNNet.forward over a darknet layer plan on the HIP backend (nnet.pas:
     275-310 selects forwardGPU per layer): every layer's output stays in a
     device buffer of its own; convolutions take BN-folded parameters
@@ -846,12 +1104,16 @@ class HipDarknet(_LstmLayers):
     softmaxBatch, logistic copy + ActivateArray, cost nothing (no truth).
     An lstm layer (``_LstmLayers``) carries c and h from one forward to the
     next until ``reset_state()``; its batch-normalized sub-layers normalize
-    by the rolling statistics."""
+    by the rolling statistics.  An rnn layer (``_RnnLayers``) likewise carries
+    its ``state``: with time_steps = 1 from call to call; with more, step i of
+    a call reads what step i of the call before left (the reference's
+    inference does not chain the steps of one call)."""
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch,
-                 lstm_fused: bool = True):
+                 lstm_fused: bool = True, rnn_fused: bool = True):
         self.hip, self.net, self.torch = hip, net, torch
         self.lstm_fused = bool(lstm_fused)
+        self.rnn_fused = bool(rnn_fused)
         B = net.batch
         dev = "cuda"
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
@@ -861,7 +1123,9 @@ class HipDarknet(_LstmLayers):
             self.out.append(self.out[-1] if alias else torch.empty(B * l.out_size, device=dev))
         self.conv_params, self.fc_params = {}, {}
         blocks = list(zip(net.param_layers(), params))
-        self._lstm_init([b for b in blocks if b[0].gate], training=False)
+        kind = lambda b: net.layers[b[0].index].kind if b[0].gate else ""  # noqa: E731
+        self._lstm_init([b for b in blocks if kind(b) == "lstm"], training=False)
+        self._rnn_init([b for b in blocks if kind(b) == "rnn"], training=False)
         for l, p in blocks:
             if l.gate:
                 continue
@@ -916,6 +1180,8 @@ class HipDarknet(_LstmLayers):
                 hip.ActivateArray(n, out, 0, l.activation)
             elif l.kind == "lstm":
                 self._lstm_forward(l, prev, False)
+            elif l.kind == "rnn":
+                self._rnn_forward(l, prev, False)
             elif l.kind == "dropout":
                 out = self.out[l.index] = prev.reshape(-1)
             elif l.kind == "softmax":
@@ -928,7 +1194,7 @@ class HipDarknet(_LstmLayers):
         return self.out
 
 
-class HipDarknetTrain(_LstmLayers):
+class HipDarknetTrain(_RnnLayers, _LstmLayers):
     """One training pass of a darknet network on the HIP backend, in the
     reference's call order: TNet.forward in training (nnet.pas:275-322; each
     layer's delta zeroed by ``cuda.scale(size, 0, delta, 1)`` before its
@@ -983,15 +1249,17 @@ class HipDarknetTrain(_LstmLayers):
     nbaselayer.pas:336-370) in the forward, the heads ``convForward``.
     ``update`` is TNNet.update (nnet.pas:371-403): ``sgdUpdate`` per layer,
     for an lstm layer on its eight sub-layers in the order wf wi wg wo uf ui
-    ug uo.  lstm layers: ``_LstmLayers``; ``lstm_fused=False`` selects the
-    reference's call sequence, call for call."""
+    ug uo, for an rnn layer on input, self, output.  lstm layers:
+    ``_LstmLayers``; rnn layers: ``_RnnLayers``; ``lstm_fused=False`` /
+    ``rnn_fused=False`` select the reference's call sequence, call for call."""
 
     LOSS_KINDS = ("softmax", "cost", "logistic")
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
-                 seed: int = 0, lstm_fused: bool = True):
+                 seed: int = 0, lstm_fused: bool = True, rnn_fused: bool = True):
         self.hip, self.net, self.torch = hip, net, torch
         self.lstm_fused = bool(lstm_fused)
+        self.rnn_fused = bool(rnn_fused)
         self.loss_scale = float(loss_scale)
         self.rng = np.random.default_rng(seed)  # default dropout seeds
         B = net.batch
@@ -1017,7 +1285,9 @@ class HipDarknetTrain(_LstmLayers):
         self.conv = {}
         ws = 1
         blocks = list(zip(net.param_layers(), params))
-        self._lstm_init([b for b in blocks if b[0].gate], training=True)
+        kind = lambda b: net.layers[b[0].index].kind if b[0].gate else ""  # noqa: E731
+        self._lstm_init([b for b in blocks if kind(b) == "lstm"], training=True)
+        self._rnn_init([b for b in blocks if kind(b) == "rnn"], training=True)
         for l, p in blocks:
             if l.gate:
                 continue
@@ -1104,6 +1374,8 @@ class HipDarknetTrain(_LstmLayers):
             elif l.kind == "lstm":
                 hip.fill(out.numel(), self.delta[l.index], 0, 0.0, 1)
                 self._lstm_forward(l, prev, True)
+            elif l.kind == "rnn":
+                self._rnn_forward(l, prev, True)
             elif l.kind == "softmax":
                 n, g = B * l.in_size, l.in_size // l.groups
                 hip.softmaxBatch(g, prev, 0, B, l.in_size, l.groups, g, 1, l.temperature, out, 0)
@@ -1184,6 +1456,9 @@ class HipDarknetTrain(_LstmLayers):
             if l.kind == "lstm":
                 self._lstm_update(l, learning_rate, momentum, decay)
                 continue
+            if l.kind == "rnn":
+                self._rnn_update(l, learning_rate, momentum, decay)
+                continue
             st = self.conv.get(l.index) or self.fc.get(l.index)
             if st is None:
                 continue
@@ -1243,6 +1518,8 @@ class HipDarknetTrain(_LstmLayers):
                 self._fc_backward(l, inp.reshape(-1), sd)
             elif l.kind == "lstm":
                 self._lstm_backward(l, inp, sd)
+            elif l.kind == "rnn":
+                self._rnn_backward(l, inp, sd)
             elif l.kind == "dropout" and sd is not None:
                 hip.backwardDropout(sd.numel(), sd, l.probability, l.scale, self.rnd[i], sd)
             elif l.kind in ("softmax", "logistic") and sd is not None:

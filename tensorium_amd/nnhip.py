@@ -566,6 +566,27 @@ class TNNHip:
             self.ctx, N, *map(_ptr, w), *map(_ptr, u), _ptr(cell_i), _ptr(cprev), _ptr(delta_i),
             _ptr(dc), *map(_ptr, dw), *map(_ptr, du)))
 
+    # -- the elementwise stage of one RNN time step (backend-specific, fused) -----
+    def rnnStateForward(self, N, H, in_slice, in_bias, in_act, self_slice, self_bias, self_act,
+                        state_prev, state_next):
+        """What TRNNLayer.rnnStepForward issues between the input / self
+        sub-layers' products and the output sub-layer (nrnnlayer.pas:148-177;
+        forwardBias, ActivateArray, fill or copy, two adds) as one launch:
+        bias (None: batch norm applied it) and activation in place on the two
+        slices, state_next = (state_prev or 0) + in + self, two roundings.
+        state_prev: None, a slice, or state_next itself."""
+        check(self.lib.tns_hip_rnn_state_forward(
+            self.ctx, N, H, _ptr(in_slice), _ptr(in_bias), int(in_act), _ptr(self_slice),
+            _ptr(self_bias), int(self_act), _ptr(state_prev), _ptr(state_next)))
+
+    def rnnDeltaBackward(self, N, delta, out, act, delta2=None, out2=None, act2=4):
+        """The clamp(delta, 1) + DeriveArray that open a connected
+        sub-layer's backward, on one slice, in place; with delta2 also the
+        copy of the result there and its own clamp + DeriveArray by out2 /
+        act2 (nrnnlayer.pas:200-214)."""
+        check(self.lib.tns_hip_rnn_delta_backward(self.ctx, N, _ptr(delta), _ptr(out), int(act),
+                                                  _ptr(delta2), _ptr(out2), int(act2)))
+
     def sum(self, N, src, offset, out):
         check(self.lib.tns_hip_sum(self.ctx, N, _ptr(src), offset, _ptr(out)))
 
