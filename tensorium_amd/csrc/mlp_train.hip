@@ -716,7 +716,8 @@ __global__ __launch_bounds__(NT) void mlp_train_kernel(MlpArgs a) {
     // the double pow of meansAndVarsDelta depends on the forward variance
     // only: the last wave evaluates it for every channel while wave 0 runs
     // the chains (it was the longest single latency of the chain thread)
-    double* st_pw = reinterpret_cast<double*>(st + ((4 * O + 1) & ~(int)1));
+    // (the doubles start on an even float of `lds`, not of `st`: 3*B*O may be odd)
+    double* st_pw = reinterpret_cast<double*>(lds + ((3 * BO + 4 * O + 1) & ~(int)1));
     if (a.bn && wid == NWAVES - 1)
       for (int o = lane; o < Oi; o += 64) {
         const float var = lay.var()[o];

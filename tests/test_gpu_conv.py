@@ -238,7 +238,8 @@ def test_yolov3_layers_batch8_implicit(hip, torch_cuda, ora, idx):
 
 @pytest.mark.parametrize("batch,C,H,F,k,s,p,act", [
     (2, 3, 17, 8, 3, 1, 1, 9), (3, 5, 12, 7, 3, 2, 1, 9), (2, 16, 9, 5, 1, 1, 0, 4),
-    (2, 6, 13, 33, 3, 1, 1, 1), (1, 32, 26, 64, 3, 2, 1, 9), (10, 4, 9, 8, 3, 1, 1, 9)])
+    (2, 6, 13, 33, 3, 1, 1, 1), (1, 32, 26, 64, 3, 2, 1, 9), (10, 4, 9, 8, 3, 1, 1, 9),
+    (1, 2, 66, 3, 3, 1, 1, 9)])  # 66^2 = 4356-pixel planes: the derivative sums' 4096-element tiles
 def test_conv_backward_matches_oracle(hip, torch_cuda, ora, batch, C, H, F, k, s, p, act):
     """delta (derived), state_delta (TN + col2im), weight_updates (NT in the
     reference's sdot order) and bias_updates (addSums order) bit-exact.  Batch
@@ -1056,7 +1057,9 @@ BN_CASES = [(2, 3, 17, 8, 3, 1, 1, 9, 1), (3, 5, 12, 7, 3, 2, 1, 9, 1), (2, 16, 
             # plane past the short-plane finish), 127^2 = 16129 (the largest
             # fused plane), 128^2 = 16384 (the first on the separate passes)
             (2, 3, 16, 5, 3, 1, 1, 9, 1), (1, 1, 127, 2, 3, 1, 1, 9, 1),
-            (1, 1, 128, 2, 3, 1, 1, 9, 1)]
+            (1, 1, 128, 2, 3, 1, 1, 9, 1),
+            # 66^2 = 4356: a 4096-element tile and a tail, rows a multiple of 4
+            (1, 2, 66, 3, 3, 1, 1, 9, 1)]
 
 
 @pytest.mark.parametrize("quirk", [0, 1])
@@ -1079,10 +1082,11 @@ BN_NS = _nonsquare([
     (2, 3, 15, 17, 5, 3, 1, 1, 9, 1),     # 255 pixels
     (1, 2, 63, 65, 3, 3, 1, 1, 9, 1),     # 4095
     (1, 2, 17, 241, 3, 3, 1, 1, 9, 1),    # 4097
+    (1, 2, 65, 67, 3, 3, 1, 1, 9, 1),     # 4355, odd: the scalar row form past one tile
     (1, 1, 127, 129, 2, 3, 1, 1, 9, 1),   # 16383
     (1, 1, 113, 145, 2, 3, 1, 1, 9, 1),   # 16385
     (1, 1, 64, 256, 2, 3, 1, 1, 9, 1)])   # 16384, a multiple of 8: the lane drop matters
-assert [c[2] * c[3] for c in BN_NS[4:]] == [255, 4095, 4097, 16383, 16385, 16384]
+assert [c[2] * c[3] for c in BN_NS[4:]] == [255, 4095, 4097, 4355, 16383, 16385, 16384]
 
 
 @pytest.mark.parametrize("quirk", [0, 1])

@@ -19,7 +19,11 @@ def dev(torch, x):
 @pytest.mark.parametrize("groups,N,bs", [(32, 64, 1), (32, 10, 1), (4, 8, 9), (2, 3, 2704),
                                          (8, 16, 2704), (3, 4, 1029), (1100, 2, 9),
                                          (8, 4, 173056), (8, 5, 169), (6, 3, 64),
-                                         (2, 3, 20011), (1, 3, 16392)])
+                                         (2, 3, 20011), (1, 3, 16392),
+                                         # 4096 <= bs < 16384, the 4096-element tiles: one
+                                         # tile + 3, two + 8 (no tail), three + 5, the last
+                                         # size of the form
+                                         (2, 3, 4099), (2, 3, 8200), (1, 2, 12293), (1, 2, 16383)])
 def test_means_vars_normalize_scale(hip, torch_cuda, ora, groups, N, bs):
     x = ora.uniform(groups * N * bs, 21, N, -2.0, 3.0)
     m, v = ora.means_and_vars(x, groups, N, bs)
@@ -42,7 +46,8 @@ def test_means_vars_normalize_scale(hip, torch_cuda, ora, groups, N, bs):
     assert np.array_equal(dx.cpu().numpy(), y2)
 
 
-@pytest.mark.parametrize("groups,N,bs", [(4, 8, 16), (8, 16, 2704), (3, 5, 24), (8, 2, 173056)])
+@pytest.mark.parametrize("groups,N,bs", [(4, 8, 16), (8, 16, 2704), (3, 5, 24), (8, 2, 173056),
+                                         (2, 3, 8200)])
 def test_means_vars_srss_quirk(hip, torch_cuda, ora, groups, N, bs):
     """TNS_OPT_SRSS_QUIRK: blocks a multiple of 8 long lose lanes 4..7 of the
     variance sum, as the reference's srss does; off by default."""
@@ -168,7 +173,8 @@ def test_init_hip_selects_the_reference_lane_drop(hiplib, torch_cuda, ora):
 
 
 BN_BWD = [(32, 64, 1), (4, 8, 9), (8, 16, 2704), (300, 3, 65), (2, 5, 1029), (3, 4, 16),
-          (8, 4, 173056), (2, 3, 43264), (8, 6, 169), (5, 2, 64), (2, 3, 20011), (1, 3, 16392)]
+          (8, 4, 173056), (2, 3, 43264), (8, 6, 169), (5, 2, 64), (2, 3, 20011), (1, 3, 16392),
+          (2, 3, 4099), (2, 3, 8200), (1, 2, 12293), (1, 2, 16383)]  # the 4096-element tiles
 
 
 @pytest.mark.parametrize("quirk", [0, 1])
@@ -207,7 +213,8 @@ def test_bn_backward_ops(hip, torch_cuda, ora, groups, N, bs, quirk):
         assert not np.array_equal(vd, vd2)
 
 
-@pytest.mark.parametrize("groups,N,bs", [(8, 4, 173056), (8, 16, 2704), (3, 5, 169), (2, 7, 65)])
+@pytest.mark.parametrize("groups,N,bs", [(8, 4, 173056), (8, 16, 2704), (3, 5, 169), (2, 7, 65),
+                                         (2, 3, 4099), (2, 3, 8200)])
 def test_conv_block_bias_sums(hip, torch_cuda, ora, groups, N, bs):
     """addSums over conv blocks (backwardBias, bs >= 64: lane-chain path)."""
     src = ora.uniform(groups * N * bs, 53, 0)
@@ -289,7 +296,7 @@ def test_fused_mlp_train_step(hip, torch_cuda, ora, bn, steps):
 
 
 @pytest.mark.parametrize("widths,acts,B", [
-    ([101, 37, 70, 24, 10], [9, 0, 6, 4], 20),   # odd widths: scalar staging, 3-tile fallback gemm
+    ([101, 37, 70, 24, 10], [9, 0, 6, 4], 20),   # odd widths; max(O) = 70: the direct 3-tile gemm
     ([64, 48, 33, 10], [1, 13, 4], 40),          # two batch tiles, hardtan
     ([784, 64, 10], [1, 4], 2),                  # smallest batch
     ([1200, 40, 10], [1, 4], 8),                 # layer 0 past 8 k-chunks: two chunks in flight
