@@ -304,6 +304,36 @@ int tns_hip_upsample(tns_ctx* ctx, int64_t aBatch, int64_t aChannels, int64_t ou
  * whole tensors, TTensor.concat ntensors.pas:12045-12061.) */
 int tns_hip_yolo_forward(tns_ctx* ctx, int64_t batch, int64_t anchors, int64_t classes,
                          int64_t hw, const float* in, float* out);
+/* TYoloLayer.forward training part (nyololayer.pas:835-1003: processBatch
+ * 500-774, deltaBox 124-202, deltaClass 204-251, averageDeltas 253-269) for
+ * one layer, on the device, bit for bit the CPU loop's delta and cost.
+ * output [batch][anchors][classes+5][h*w] is what tns_hip_yolo_forward left;
+ * truth [batch][maxBoxes][6] on the device, rows x, y, w, h, class, track_id,
+ * a row with x == 0 ends an image's list; mask (anchors entries) and biases
+ * (2*total floats) are HOST arrays, copied before the call returns.  Writes
+ * delta (same shape as output, every element: delta.fill(0) is part of the
+ * call), cost[0] = delta.sumSquares() (TTensor.sumSqr, ntensors.pas:9333-9341,
+ * the ascending single chain), stats[2*b] = count and stats[2*b+1] = tot_iou
+ * of image b (stats may be null), and adds to counters[0] = net.totalBBox and
+ * counters[1] = net.rewrittenBBox (device int64).  A NaN or infinite
+ * objectness in output is set to 0 where the reference does (an image with at
+ * least one truth of a valid class).  Built: iou_loss=mse, iou_thresh_kind=iou,
+ * scale_x_y=1; not built: focal_loss, objectness_smooth, label_smooth_eps,
+ * new_coords, counters_per_class, map, embedding_layer, [net] adversarial and
+ * the bad-label rejection block (896-990); the GIoU/DIoU/CIoU statistics,
+ * avg_* / recall, labels and classIds are not computed.  Departure: a truth
+ * whose cell trunc(x*w), trunc(y*h) lies outside the grid is skipped in the
+ * truth pass (the reference writes out of bounds).  TNS_ERR_ARG, before
+ * anything is launched or written: a negative size, netW / netH below 1, a
+ * null operand (stats excepted), a mask entry outside [0, total), maxBoxes
+ * outside [1, 2048], anchors or total above 32, batch above 65535, a buffer
+ * beyond 2^31 elements. */
+int tns_hip_yolo_loss(tns_ctx* ctx, int64_t batch, int64_t anchors, int64_t classes, int64_t h,
+                      int64_t w, int64_t total, const int64_t* mask, const float* biases,
+                      int64_t maxBoxes, int64_t netW, int64_t netH, float ignoreThresh,
+                      float truthThresh, float iouThresh, float iouNormalizer,
+                      float objNormalizer, float* output, const float* truth, float* delta,
+                      float* cost, float* stats, int64_t* counters);
 
 /* ---- max / local-average pooling (TMaxPoolLayer, nMaxPoolLayer.pas) ----- */
 /* Geometry, shared by the four entries: input [aBatch][c][h][w], output

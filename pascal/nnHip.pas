@@ -188,6 +188,12 @@ function tns_hip_upsample(ctx: PTnsCtx; aBatch, aChannels, outHeight, outWidth: 
   zeroIn: longint): longint; cdecl; external libtns;
 function tns_hip_yolo_forward(ctx: PTnsCtx; batch, anchors, classes, hw: int64; input,
   output: THipMem): longint; cdecl; external libtns;
+{ TYoloLayer.forward, training part (nyololayer.pas:835-1003): mask (SizeInt) and
+  biases are host arrays, counters a device int64[2] (totalBBox, rewrittenBBox) }
+function tns_hip_yolo_loss(ctx: PTnsCtx; batch, anchors, classes, h, w, total: int64;
+  mask: PInt64; biases: PSingle; maxBoxes, netW, netH: int64; ignoreThresh, truthThresh,
+  iouThresh, iouNormalizer, objNormalizer: single; output, truth, delta, cost,
+  stats: THipMem; counters: PInt64): longint; cdecl; external libtns;
 
 { max / local-average pooling; indexes = TSizeIntTensor's device data }
 function tns_hip_maxpool_forward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; input: THipMem;
@@ -366,6 +372,7 @@ type
     procedure backwardMaxPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const indexes, delta: TCUMem; const h: SizeInt = 0; const w: SizeInt = 0; const stride_x: SizeInt = 0; const stride_y: SizeInt = 0; const padding: SizeInt = 0; const kernelSize: SizeInt = 0);
     procedure forwardAvgPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; output: TCUMem);
     procedure backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const delta: TCUMem; const h, w, stride_x, stride_y, padding, kernelSize: SizeInt);
+    procedure yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
     procedure upSample(const aBatch, aChannels, outHeight, outWidth: SizeInt; const &in: TCUMem; const stride: SizeInt; const isForward: longint; const scale: T; const &out: TCUMem; const zeroIn: integer = 0);
@@ -647,6 +654,17 @@ procedure TNNHip<T>.backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; out
 begin
   check(tns_hip_avgpool_backward(FCtx, aBatch, outC, outH, outW, THipMem(output), THipMem(delta),
     h, w, stride_x, stride_y, padding, kernelSize))
+end;
+
+procedure TNNHip<T>.yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);
+begin
+  { mask = layer.mask.data, biases = layer.biases.data (host); output as
+    tns_hip_yolo_forward left it; stats may be nil; counters: two int64 on the
+    device, net.totalBBox and net.rewrittenBBox, added to }
+  check(tns_hip_yolo_loss(FCtx, batch, anchors, classes, h, w, total, PInt64(mask), biases,
+    maxBoxes, netW, netH, ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer,
+    THipMem(output), THipMem(truth), THipMem(delta), THipMem(cost), THipMem(stats),
+    PInt64(counters)))
 end;
 
 procedure TNNHip<T>.im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);

@@ -194,6 +194,11 @@ PROTOTYPES.update({
                                                       fptr, i64, i64, i64]),
     "tns_set_op_devices": (C.c_int, [C.POINTER(i32), i32]),
     "tns_hip_yolo_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr]),
+    # the yolo loss: mask (int64) and biases are host arrays; output, truth,
+    # delta, cost, stats device floats; counters a device int64[2]
+    "tns_hip_yolo_loss": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, C.POINTER(i64),
+                                    C.POINTER(f32), i64, i64, i64, f32, f32, f32, f32, f32, fptr,
+                                    fptr, fptr, fptr, fptr, vp]),
     # pooling: the indexes operand is an int64 device buffer
     "tns_hip_maxpool_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, i64, i64, i64, i64, i64,
                                           i64, i64, vp, fptr]),

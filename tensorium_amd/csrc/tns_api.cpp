@@ -125,7 +125,7 @@ struct tns_ctx {
 namespace {
 
 enum { SLOT_COL = 0, SLOT_STAGE1 = 1, SLOT_STAGE2 = 2, SLOT_STAGE3 = 3, SLOT_DW = 4, SLOT_BN = 5,
-       SLOT_MLP = 6, SLOT_WT = 7, SLOT_COL_DX = 8, /* 9: unused */ SLOT_RES_A = 10,
+       SLOT_MLP = 6, SLOT_WT = 7, SLOT_COL_DX = 8, SLOT_YOLO = 9, SLOT_RES_A = 10,
        SLOT_RES_B = 11, SLOT_COUNT = 12 };
 static_assert(SLOT_COUNT == tns_ctx::kSlots, "one scratch buffer per slot");
 
@@ -1277,6 +1277,61 @@ int tns_hip_yolo_forward(tns_ctx* c, int64_t batch, int64_t anchors, int64_t cla
       (batch * anchors * hw > 0 && (!in || !out)))
     return set_error(TNS_ERR_ARG, "yolo: bad args");
   return hip_status(launch_yolo(batch, (int)anchors, (int)classes, hw, in, out, c->stream), "yolo");
+}
+
+int tns_hip_yolo_loss(tns_ctx* c, int64_t batch, int64_t anchors, int64_t classes, int64_t h,
+                      int64_t w, int64_t total, const int64_t* mask, const float* biases,
+                      int64_t maxBoxes, int64_t netW, int64_t netH, float ignoreThresh,
+                      float truthThresh, float iouThresh, float iouNormalizer, float objNormalizer,
+                      float* output, const float* truth, float* delta, float* cost, float* stats,
+                      int64_t* counters) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (batch < 0 || anchors < 0 || classes < 0 || h < 0 || w < 0 || total < 0 || netW < 1 ||
+      netH < 1)
+    return set_error(TNS_ERR_ARG, "yolo loss: negative size, or a network extent below 1");
+  if (maxBoxes < 1 || maxBoxes > kYoloMaxBoxes)
+    return set_error(TNS_ERR_ARG, "yolo loss: maxBoxes %lld outside [1, %d]", (long long)maxBoxes,
+                     kYoloMaxBoxes);
+  if (anchors > kYoloMaxAnchors || total > kYoloMaxAnchors)
+    return set_error(TNS_ERR_ARG, "yolo loss: more than %d anchors", kYoloMaxAnchors);
+  const int64_t lim = 0x3fffffff;
+  if (batch > 65535 || classes > lim || h > lim || w > lim || netW > (1 << 24) ||
+      netH > (1 << 24) || h * w > lim || batch * anchors > lim ||
+      batch * anchors * (classes + 5) > 0x7fff0000 / std::max<int64_t>(h * w, 1))
+    return set_error(TNS_ERR_ARG, "yolo loss: batch beyond 65535, or a buffer beyond 2^31 elements");
+  if (!output || !truth || !delta || !cost || !counters || (anchors > 0 && !mask) ||
+      (total > 0 && !biases))
+    return set_error(TNS_ERR_ARG, "yolo loss: null operand");
+  YoloLossParams p{};
+  for (int64_t i = 0; i < anchors; ++i) {
+    if (mask[i] < 0 || mask[i] >= total)
+      return set_error(TNS_ERR_ARG, "yolo loss: mask[%lld] = %lld outside [0, %lld)", (long long)i,
+                       (long long)mask[i], (long long)total);
+    p.mask[i] = (int)mask[i];
+  }
+  for (int64_t i = 0; i < 2 * total; ++i) p.biases[i] = biases[i];
+  p.batch = (int)batch, p.n = (int)anchors, p.classes = (int)classes, p.h = (int)h, p.w = (int)w;
+  p.total = (int)total, p.maxBoxes = (int)maxBoxes, p.netW = (int)netW, p.netH = (int)netH;
+  p.ignoreThresh = ignoreThresh, p.truthThresh = truthThresh, p.iouThresh = iouThresh;
+  p.iouNormalizer = iouNormalizer, p.objNormalizer = objNormalizer;
+  const int64_t n = batch * anchors * (classes + 5) * h * w;
+  if (int r = check_ops(c,
+                        {span(delta, n), span(output, n), span(cost, 1), span(stats, 2 * batch),
+                         span(reinterpret_cast<float*>(counters), 4)},
+                        {span(truth, batch * maxBoxes * 6)}))
+    return r;
+  if (n == 0) {  // nothing to sum, no truth to count
+    if (hipError_t e = launch_fill(1, cost, 0.0f, 1, c->stream); e != hipSuccess)
+      return hip_status(e, "yolo loss");
+    return hip_status(stats ? launch_fill(2 * batch, stats, 0.0f, 1, c->stream) : hipSuccess,
+                      "yolo loss");
+  }
+  float* scratch = nullptr;
+  if (int r = ensure_scratch(c, SLOT_YOLO, yolo_loss_scratch_floats(n), &scratch)) return r;
+  return hip_status(launch_yolo_loss(p, output, truth, delta, cost, stats,
+                                     reinterpret_cast<unsigned long long*>(counters), scratch,
+                                     c->stream),
+                    "yolo loss");
 }
 
 // TNNCuda.forwardMaxPool / backwardMaxPool (nncuda.pas:132-133) and the local

@@ -352,6 +352,22 @@ hipError_t launch_inverse_sqrt(int64_t n, const float* src, float* dst, int64_t 
                                hipStream_t s);
 hipError_t launch_yolo(int64_t batch, int anchors, int classes, int64_t hw, const float* in,
                        float* out, hipStream_t s);
+// yolo_loss.hip: the training part of TYoloLayer.forward for one layer.  n =
+// len(mask) anchors of `total`; mask and biases (2*total) by value, so at
+// most kYoloMaxAnchors of each.  scratch: yolo_loss_scratch_floats(elements
+// of delta) floats.  counters: {totalBBox, rewrittenBBox}, added to.
+constexpr int kYoloMaxAnchors = 32;
+constexpr int kYoloMaxBoxes = 2048;  // the truth rows of one image fit the LDS
+struct YoloLossParams {
+  int batch, n, classes, h, w, total, maxBoxes, netW, netH;
+  float ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer;
+  int mask[kYoloMaxAnchors];
+  float biases[2 * kYoloMaxAnchors];
+};
+int64_t yolo_loss_scratch_floats(int64_t n);
+hipError_t launch_yolo_loss(const YoloLossParams& p, float* out, const float* truth, float* delta,
+                            float* cost, float* stats, unsigned long long* counters,
+                            float* scratch, hipStream_t s);
 hipError_t launch_bias_activate(float* dst, int64_t nFilters, int64_t blockSize,
                                 const float* bias, int64_t batch, int act, hipStream_t s);
 hipError_t launch_derive(const float* x, int64_t n, int act, float* delta, hipStream_t s);

@@ -114,6 +114,18 @@ class Layer:
     hidden: int = 0            # rnn: the state's width (filters is its output's)
     self_activation: int = ACT["LINEAR"]  # rnn: the self sub-layer's (logistic=1: LOGISTIC)
     shortcut: bool = False     # rnn: TRNNLayer.isShortcut, a public field no cfg key sets
+    # yolo, what its training loss reads (parseYolo, nparser.pas:516-643)
+    mask: tuple = ()           # the anchors of this scale, indices into `total`
+    total: int = 0             # num=
+    biases: tuple = ()         # anchors= as float32 values, 2*total of them (0.5 where absent)
+    max_boxes: int = 200       # max=
+    ignore_thresh: float = 0.5  # the thresholds and normalizers: float32 values
+    truth_thresh: float = 1.0
+    iou_thresh: float = 1.0
+    iou_normalizer: float = 0.75
+    obj_normalizer: float = 1.0
+    delta_normalizer: float = 1.0
+    unbuilt: tuple = ()        # the keys set that the device loss does not build
 
     def __post_init__(self):
         self.stride_x = self.stride_x or self.stride
@@ -139,6 +151,51 @@ def _flag(sec: Section, key: str) -> bool:
         return int(str(sec.get(key, "0")).strip()) != 0
     except ValueError:
         return False
+
+
+def _f32(sec: Section, key: str, default: float) -> float:
+    """getFloat into a single field: the value as float32."""
+    return float(np.float32(float(str(sec.get(key, default)).strip())))
+
+
+def _yolo_loss_fields(sec: Section, mask: list) -> dict:
+    """The [yolo] keys the training loss reads, with parseYolo's defaults
+    (nparser.pas:516-643), and in ``unbuilt`` the keys whose setting the
+    device loss does not build (HipDarknetTrain(yolo_loss=True) refuses
+    them; inference and set_yolo_deltas training do not read them)."""
+    total = sec.int("num", 1)
+    vals = [v for v in str(sec.get("anchors", "")).split(",") if v.strip()]
+    biases = [np.float32(0.5)] * (2 * total)  # TYoloLayer.Create: biases.fill(0.5)
+    for k in range(min(len(vals), 2 * total)):
+        biases[k] = np.float32(float(vals[k].strip()))
+    unbuilt = []
+    if str(sec.get("iou_loss", "mse")).strip() != "mse":
+        unbuilt.append("iou_loss")
+    if str(sec.get("iou_thresh_kind", "iou")).strip() != "iou":
+        unbuilt.append("iou_thresh_kind")
+    unbuilt += [k for k in ("focal_loss", "objectness_smooth", "new_coords") if _flag(sec, k)]
+    if _f32(sec, "label_smooth_eps", 0.0) != 0.0:
+        unbuilt.append("label_smooth_eps")
+    if _f32(sec, "scale_x_y", 1.0) != 1.0:
+        unbuilt.append("scale_x_y")
+    unbuilt += [k for k in ("counters_per_class", "map") if str(sec.get(k, "")).strip()]
+    if sec.int("embedding_layer", 999999) != 999999:
+        unbuilt.append("embedding_layer")
+    return dict(mask=tuple(int(m) for m in mask), total=total,
+                biases=tuple(float(v) for v in biases), max_boxes=sec.int("max", 200),
+                ignore_thresh=_f32(sec, "ignore_thresh", 0.5),
+                truth_thresh=_f32(sec, "truth_thresh", 1.0),
+                iou_thresh=_f32(sec, "iou_thresh", 1.0),
+                iou_normalizer=_f32(sec, "iou_normalizer", 0.75),
+                obj_normalizer=_f32(sec, "obj_normalizer", 1.0),
+                delta_normalizer=_f32(sec, "delta_normalizer", 1.0), unbuilt=tuple(unbuilt))
+
+
+# [net] keys that switch on what the device yolo loss does not build: the
+# adversarial branch and the bad-label rejection block (nyololayer.pas:589-613,
+# 896-990; nparser.pas:975-977)
+_NET_YOLO_UNBUILT = ("adversarial", "adversarial_lr", "equidistant_point",
+                     "badlabels_rejection_percentage", "num_sigmas_reject_badlabels")
 
 
 # kinds that read params.c / h / w, which the reference leaves stale after a
@@ -170,6 +227,8 @@ class Network:
             raise ValueError(f"[net] time_steps={self.time_steps}")
         self.batch = batch if batch is not None else net.int("batch", 1) * self.time_steps
         self.h, self.w, self.c = net.int("height"), net.int("width"), net.int("channels", 3)
+        # the [net] keys set that the device yolo loss does not build
+        self.yolo_unbuilt = tuple(k for k in _NET_YOLO_UNBUILT if _f32(net, k, 0.0) != 0.0)
         self.layers: list[Layer] = []
         c, h, w = self.c, self.h, self.w
         flat = False  # a [connected] has been planned: c, h, w are the parser's no longer
@@ -214,7 +273,8 @@ class Network:
             elif sec.kind == "yolo":
                 mask = [m for m in sec.get("mask", "").split(",") if m.strip()]
                 classes = sec.int("classes", 20)
-                lay = Layer(i, "yolo", c, h, w, c, h, w, anchors=len(mask), classes=classes)
+                lay = Layer(i, "yolo", c, h, w, c, h, w, anchors=len(mask), classes=classes,
+                            **_yolo_loss_fields(sec, mask))
                 if c != len(mask) * (classes + 5):
                     raise ValueError(f"yolo layer {i}: {c} channels for {len(mask)} anchors")
             elif sec.kind in ("maxpool", "max", "local_avgpool"):
@@ -1214,9 +1274,11 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
     * upsample (TUpSampleLayer.backwardGPU, nupsamplelayer.pas:214-228):
       ``upSample(..., isForward = 0)`` accumulating into state.delta;
     * yolo (TYoloLayer.backwardGPU, nyololayer.pas:1112-1125): ``axpy`` of its
-      delta (scaled by lossScale*deltaNormalizer) into state.delta.  The yolo
-      loss that fills that delta during the training forward is out of scope
-      (DESIGN.md); ``set_yolo_deltas`` supplies it;
+      delta (scaled by lossScale*deltaNormalizer) into state.delta.  With
+      ``yolo_loss=True`` the training forward fills that delta and the
+      layer's cost from the truth boxes (``yoloLoss``, TYoloLayer.forward
+      under state.isTraining, nyololayer.pas:835-1003); without it
+      ``set_yolo_deltas`` supplies the delta;
     * maxpool / local_avgpool (TMaxPoolLayer.backwardGPU, nMaxPoolLayer.pas:
       689-706; CPU loops 501-542): ``backwardMaxPool`` with the indexes its
       forward stored, or ``backwardAvgPool``, accumulating into state.delta;
@@ -1256,11 +1318,25 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
     LOSS_KINDS = ("softmax", "cost", "logistic")
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
-                 seed: int = 0, lstm_fused: bool = True, rnn_fused: bool = True):
+                 seed: int = 0, lstm_fused: bool = True, rnn_fused: bool = True,
+                 yolo_loss: bool = False):
         self.hip, self.net, self.torch = hip, net, torch
         self.lstm_fused = bool(lstm_fused)
         self.rnn_fused = bool(rnn_fused)
         self.loss_scale = float(loss_scale)
+        self.yolo_loss = bool(yolo_loss)
+        yolos = [l for l in net.layers if l.kind == "yolo"]
+        if self.yolo_loss:
+            # what the device loss does not build is refused here, and only
+            # here: inference and set_yolo_deltas training take these cfgs
+            bad = [f"[net] {k}" for k in net.yolo_unbuilt]
+            bad += [f"[yolo] layer {l.index} {k}" for l in yolos for k in l.unbuilt]
+            if bad:
+                raise ValueError("yolo_loss=True: the device loss does not build "
+                                 + ", ".join(bad))
+            if len({l.max_boxes for l in yolos}) > 1:
+                raise ValueError("yolo_loss=True: the [yolo] layers disagree on max: "
+                                 f"{[l.max_boxes for l in yolos]} (one truth tensor feeds all)")
         self.rng = np.random.default_rng(seed)  # default dropout seeds
         B = net.batch
         dev = "cuda"
@@ -1278,6 +1354,14 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
                      for l in net.layers if l.kind in ("softmax", "logistic")}
         self.costs = {l.index: torch.zeros(1, device=dev)
                       for l in net.layers if l.kind in self.LOSS_KINDS}
+        # the device yolo loss: cost[1] and the per-image {count, tot_iou} of
+        # every yolo layer, and the network's {totalBBox, rewrittenBBox}
+        self.yolo_stats = {}
+        if self.yolo_loss:
+            for l in yolos:
+                self.costs[l.index] = torch.zeros(1, device=dev)
+                self.yolo_stats[l.index] = torch.zeros(2 * B, device=dev)
+            self.yolo_counters = torch.zeros(2, dtype=torch.int64, device=dev)
         self.fc = {}
         # a maxpool's indexes (TSizeIntTensor, int64): filled by its forward
         self.indexes = {l.index: torch.zeros(B * l.out_size, dtype=torch.int64, device=dev)
@@ -1314,7 +1398,8 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
         """TNet.forward with state.isTraining (BN statistics of the batch,
         rolling statistics updated with bnMomentum 0.1, connected layers
         0.05).  truth: device tensor of the loss layers' size (state.truth),
-        or None (no loss is computed).  seeds: one integer in [0, 2^32) per
+        or None (no loss is computed); with ``yolo_loss`` the truth boxes
+        [batch, max_boxes*6], the same tensor for every yolo layer.  seeds: one integer in [0, 2^32) per
         dropout layer, in layer order; by default drawn in [0, 2^28), the
         reference's random($10000000), from the generator seeded at
         construction."""
@@ -1363,6 +1448,15 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
                 hip.upSample(B, l.c, l.h, l.w, prev, l.stride, 1, 1.0, out)
             elif l.kind == "yolo":
                 hip.yoloForward(B, l.anchors, l.classes, l.h * l.w, prev, out)
+                if self.yolo_loss and truth is not None:
+                    if truth.numel() != B * l.max_boxes * 6:
+                        raise ValueError(f"truth has {truth.numel()} floats, batch {B} x max "
+                                         f"{l.max_boxes} x 6 expected")
+                    hip.yoloLoss(B, l.anchors, l.classes, l.h, l.w, l.total, l.mask, l.biases,
+                                 l.max_boxes, self.net.w, self.net.h, l.ignore_thresh,
+                                 l.truth_thresh, l.iou_thresh, l.iou_normalizer, l.obj_normalizer,
+                                 out, truth, self.delta[l.index], self.costs[l.index],
+                                 self.yolo_stats[l.index], self.yolo_counters)
             elif l.kind == "maxpool":
                 hip.forwardMaxPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
                                    l.stride_y, l.pad, l.size, self.indexes[l.index], out)
@@ -1507,7 +1601,9 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
             elif l.kind == "upsample":
                 hip.upSample(B, l.c, l.h, l.w, sd, l.stride, 0, 1.0, d)
             elif l.kind == "yolo":
-                hip.axpy(sd.numel(), self.loss_scale, d, 0, 1, sd, 0, 1)
+                # lossScale*deltaNormalizer, a single product (nyololayer.pas:1119)
+                hip.axpy(sd.numel(), float(np.float32(self.loss_scale)
+                                           * np.float32(l.delta_normalizer)), d, 0, 1, sd, 0, 1)
             elif l.kind == "maxpool" and sd is not None:
                 hip.backwardMaxPool(B, l.out_c, l.out_h, l.out_w, sd, self.indexes[i], d, l.h, l.w,
                                     l.stride_x, l.stride_y, l.pad, l.size)

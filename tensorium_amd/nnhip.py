@@ -305,6 +305,26 @@ class TNNHip:
         check(self.lib.tns_hip_yolo_forward(self.ctx, batch, anchors, classes, hw, _ptr(inp),
                                             _ptr(out)))
 
+    def yoloLoss(self, batch, anchors, classes, h, w, total, mask, biases, maxBoxes, netW, netH,
+                 ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer, output, truth,
+                 delta, cost, stats=None, counters=None):
+        """TYoloLayer.forward's training part for one layer (tns_hip_yolo_loss).
+        mask / biases: host sequences (len anchors / 2*total); output, truth,
+        delta, cost, stats: device float tensors; counters: a device int64[2]
+        (totalBBox, rewrittenBBox), added to."""
+        mask = [int(m) for m in mask]
+        biases = [float(v) for v in biases]
+        if len(mask) != anchors or len(biases) != 2 * total:
+            raise TnsError(f"yoloLoss: {len(mask)} mask entries for {anchors} anchors, "
+                           f"{len(biases)} biases for total={total}")
+        m = (C.c_int64 * max(len(mask), 1))(*mask)
+        bs = (C.c_float * max(len(biases), 1))(*biases)
+        check(self.lib.tns_hip_yolo_loss(
+            self.ctx, batch, anchors, classes, h, w, total, m, bs, maxBoxes, netW, netH,
+            float(ignoreThresh), float(truthThresh), float(iouThresh), float(iouNormalizer),
+            float(objNormalizer), _ptr(output), _ptr(truth), _ptr(delta), _ptr(cost), _ptr(stats),
+            _iptr(counters)))
+
     # -- layer drivers ------------------------------------------------------------
     def conv2d(self, batch, C_, H, W, input, weights, filters, kH, kW, wPadding, hPadding,
                xStride, yStride, xDilation, yDilation, workspace, out):
