@@ -17,7 +17,7 @@
 // C*k^2*oh*ow col matrix round trip through HBM and the col2im pass.
 //
 // The weights are read as Wt[t][f][c] (a transposed copy made once per call,
-// tns_api.cpp) so a tap's A tile rows are contiguous; k-tiles of 32 filters,
+// conv_api.cpp) so a tap's A tile rows are contiguous; k-tiles of 32 filters,
 // two LDS stages, one barrier per k-tile; the chains of all taps run back to
 // back through one pipeline (chunk q = t * ceil(F/32) + f-chunk).
 #include <algorithm>

@@ -4,10 +4,9 @@
 //   * boundary A: op-table drop-ins with host pointers (cblas_sgemm & co,
 //     ntensors.pas:345-385) staging through device scratch owned here;
 //   * boundary B: the TNNCuda<T>-shaped device API (nncuda.pas:35-157);
-//   * layer drivers: TTensor.Conv2D (ntensors.pas:8252-8349) and
-//     TConvolutionalLayer.forward/forwardGPU (nConvolutionLayer.pas:457-569,
-//     1022-1153).
-// Nothing here falls back to the CPU: every compute entry point launches a
+//   * the options (tns_set_option), contexts and the error channel.
+// The convolutional layer drivers are in conv_api.cpp; what both files share
+// is in tns_ctx.hpp.  Nothing here falls back to the CPU: every compute entry point launches a
 // gfx950 kernel or fails with a status.
 #include <hip/hip_runtime.h>
 
@@ -24,41 +23,19 @@
 #include <string>
 #include <tuple>
 
-#include "tns_internal.hpp"
+#include "tns_ctx.hpp"
 
 namespace tns {
 
 static thread_local std::string g_err;
 static tns_error_hook_t g_hook = nullptr;
-static int64_t g_strict_beta0 = 1;
-static int64_t g_nt_sdot = 1;
-static int64_t g_dx_fused = 1;
-// conv backward col = W^T . delta: -1 conv_tile4's k-major-A forms where
-// they apply, -2 the TN GEMM, v >= 0 form v (TNS_OPT_DX_TILE)
-static int64_t g_dx_tile = -1;
-static int64_t g_dx_conv = -1;
-static int64_t g_dw_res = -1;
-// state.delta of the 1x1 / stride-1 layers on conv1x1.hip (W^T over the delta
-// planes, the col2im add in the epilogue) where conv1x1_pick takes the shape;
-// TNS_DX_C1=0 (A/B): the TN product / conv_dx forms
-static bool g_dx_c1 = !(getenv("TNS_DX_C1") && getenv("TNS_DX_C1")[0] == '0');
-// the BN conv backward as one chain pass + normalizeDelta (launch_bn_backward_fused);
-// TNS_BN_FUSED=0 (A/B): the three-pass form
-static bool g_bn_fused = !(getenv("TNS_BN_FUSED") && getenv("TNS_BN_FUSED")[0] == '0');
-// conv backward dW with the im2col matrix generated in the staging
-// (dw_tile.hip): -1 by measured shape, -2 never, v >= 0 form v (TNS_OPT_DW_TILE)
-static int64_t g_dw_tile = -1;
-// conv backward: dW and state.delta concurrently on two streams (TNS_OPT_BWD_OVERLAP)
-static int64_t g_bwd_overlap = 1;
-static int64_t g_derive_sums = 0;
-// TNS_OPT_SCRATCH_CAP: largest context scratch buffer in floats (0 = none);
-// a larger request fails as an allocation failure would (tests reach the
-// fallback paths with it)
-static int64_t g_scratch_cap = 0;
-static int64_t g_tt_exact = 1;
-static int64_t g_srss_quirk = 0;
-static int64_t g_conv_variant = -1;
-static int64_t g_conv_pad = -1;
+static bool env_on(const char* name) { return !(getenv(name) && getenv(name)[0] == '0'); }
+Options g_opt = [] {
+  Options o;
+  o.dx_c1 = env_on("TNS_DX_C1");
+  o.bn_fused = env_on("TNS_BN_FUSED");
+  return o;
+}();
 
 int set_error(int code, const char* fmt, ...) {
   char buf[1024];
@@ -77,320 +54,13 @@ const char* hip_err_str(hipError_t e) { return hipGetErrorString(e); }
 
 using namespace tns;
 
-struct tns_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  // device scratch, one buffer per SLOT_* below (im2col workspace, host-API
-  // staging, dW partial sums, batch-norm block results, ...)
-  static constexpr int kSlots = 12;
-  float* scratch[kSlots] = {};
-  size_t scratch_elems[kSlots] = {};
-  // telemetry (TTensorMetrics-style, nopmetrics.pas:25-44)
-  bool telemetry = false;
-  double op_ms[TNS_OP_COUNT] = {0};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::mutex mu;  // serialises host-API use of one context
-  // host-pointer pipeline: copy stream and per-chunk events
-  hipStream_t copy_stream = nullptr;
-  std::vector<hipEvent_t> pipe_ev;
-  // conv backward: state.delta's chain (TN + col2im) runs on this side
-  // stream while the dW product runs on `stream` (fork / join events)
-  hipStream_t aux_stream = nullptr;
-  // the joined overlap's side stream (TNS_OPT_BWD_OVERLAP = 1: state.delta's
-  // chain beside the call's dW, joined before the call returns) at the
-  // context stream's priority; aux_stream, the pipelined dW products' stream,
-  // sits at the lowest
-  hipStream_t ovl_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // TNS_OPT_BWD_OVERLAP = 2: dW products left running on aux_stream past the
-  // call's return; the next call of any other entry point joins them first
-  bool side_pending = false;
-  hipStream_t home_stream = nullptr;  // the context's stream while `stream` is aux
-  // the pending dW products' operand ranges: read (delta, input) and written
-  // (weight_updates; the caller's workspace when the dW's im2col fills it).
-  // A later call whose work on `stream` writes a read range, or touches a
-  // written one, joins the side stream first; so does a call that takes a
-  // scratch slot the side stream uses (side_slots)
-  struct PendingDw {
-    uintptr_t lo[2], hi[2];    // read by the dW
-    uintptr_t wlo[2], whi[2];  // written by the dW
-  };
-  std::vector<PendingDw> pending;
-  uint32_t side_slots = 0;
-  // implicit-GEMM conv k-tables, one per (C, H, W, kH, kW, dY, dX)
-  std::map<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>, int*> ktabs;
-};
-
 namespace {
-
-enum { SLOT_COL = 0, SLOT_STAGE1 = 1, SLOT_STAGE2 = 2, SLOT_STAGE3 = 3, SLOT_DW = 4, SLOT_BN = 5,
-       SLOT_MLP = 6, SLOT_WT = 7, SLOT_COL_DX = 8, SLOT_YOLO = 9, SLOT_RES_A = 10,
-       SLOT_RES_B = 11, SLOT_COUNT = 12 };
-static_assert(SLOT_COUNT == tns_ctx::kSlots, "one scratch buffer per slot");
-
-int join_side(tns_ctx* c);
-
-// scratch buffer `slot` of at least `elems` floats.  side: the caller is the
-// pipelined conv backward taking a slot for the dW it queues behind the
-// pending ones on the side stream (no join); any other caller of a slot the
-// side stream still uses joins it first
-int ensure_scratch(tns_ctx* c, int slot, int64_t elems, float** out, bool side = false) {
-  if (elems < 1) elems = 1;
-  if (!side && c->side_pending && (c->side_slots >> slot & 1u) && c->stream != c->aux_stream)
-    if (int r = join_side(c)) return r;
-  if (g_scratch_cap > 0 && elems > g_scratch_cap)
-    return set_error(TNS_ERR_NOMEM, "scratch slot %d: %lld floats exceed the cap of %lld", slot,
-                     (long long)elems, (long long)g_scratch_cap);
-  if ((size_t)elems > c->scratch_elems[slot]) {
-    if (c->scratch[slot]) {
-      hipStreamSynchronize(c->stream);
-      if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
-      if (c->ovl_stream) hipStreamSynchronize(c->ovl_stream);
-      if (c->home_stream) hipStreamSynchronize(c->home_stream);
-      hipFree(c->scratch[slot]);
-      c->scratch[slot] = nullptr;
-      c->scratch_elems[slot] = 0;
-    }
-    hipError_t e = hipMalloc(&c->scratch[slot], (size_t)elems * sizeof(float));
-    if (e != hipSuccess) {
-      c->scratch[slot] = nullptr;
-      // (clear HIP's sticky last error: the launch helpers report
-      // hipGetLastError(), and a caller that falls back after this failure
-      // must not see it on its first launch)
-      hipGetLastError();
-      return set_error(TNS_ERR_NOMEM, "hipMalloc(%lld floats) failed: %s", (long long)elems,
-                       hipGetErrorString(e));
-    }
-    c->scratch_elems[slot] = (size_t)elems;
-  }
-  *out = c->scratch[slot];
-  return TNS_OK;
-}
-
-// give a scratch buffer back (every stream that may still use it drained)
-void release_scratch(tns_ctx* c, int slot) {
-  if (!c->scratch[slot]) return;
-  hipStreamSynchronize(c->stream);
-  if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
-  if (c->ovl_stream) hipStreamSynchronize(c->ovl_stream);
-  if (c->home_stream) hipStreamSynchronize(c->home_stream);
-  hipFree(c->scratch[slot]);
-  c->scratch[slot] = nullptr;
-  c->scratch_elems[slot] = 0;
-}
-
-// the conv backward's side stream and its fork / join events, created
-// together on the context's device; false (nothing kept) if any of them
-// cannot be created, and the caller runs its sequential schedule
-bool ensure_side_stream(tns_ctx* c) {
-  if (c->aux_stream && c->ovl_stream && c->ev_fork && c->ev_join) return true;
-  int prev = -1;
-  hipGetDevice(&prev);
-  // the pipelined dW products' stream (off the critical path) at the lowest
-  // queue priority and the context's stream at the highest: the context's
-  // work is dispatched first where both wait for CU room (YOLOv3 training
-  // backward 17.96 -> 17.81 ms with the chain waves' issue priority,
-  // batchnorm.hip; TNS_STREAM_PRIO=0 turns it off).  The joined overlap
-  // waits for both halves of a call, so its stream keeps the default
-  // priority (at the lowest, the joined conv backward lost 0.25 ms)
-  int least = 0, greatest = 0;
-  const char* sp = getenv("TNS_STREAM_PRIO");
-  const bool prio = !(sp && sp[0] == '0') &&
-                    hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-  bool ok = hipSetDevice(c->device) == hipSuccess &&
-            (prio ? hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, least)
-                  : hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking)) == hipSuccess &&
-            hipStreamCreateWithFlags(&c->ovl_stream, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    if (c->aux_stream) hipStreamDestroy(c->aux_stream);
-    if (c->ovl_stream) hipStreamDestroy(c->ovl_stream);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
-    c->aux_stream = c->ovl_stream = nullptr;
-    c->ev_fork = c->ev_join = nullptr;
-    hipGetLastError();
-  }
-  if (prev >= 0) hipSetDevice(prev);
-  return ok;
-}
-
-struct OpTimer {
-  tns_ctx* c;
-  int op;
-  explicit OpTimer(tns_ctx* c_, int op_) : c(c_), op(op_) {
-    if (c->telemetry) hipEventRecord(c->ev0, c->stream);
-  }
-  ~OpTimer() {
-    if (c->telemetry) {
-      hipEventRecord(c->ev1, c->stream);
-      hipEventSynchronize(c->ev1);
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, c->ev0, c->ev1);
-      c->op_ms[op] += ms;
-    }
-  }
-};
-
-// the dW products a pipelined conv backward (TNS_OPT_BWD_OVERLAP = 2) left
-// on the side stream: the context's stream waits for them from here on
-int join_side(tns_ctx* c) {
-  if (!c->side_pending) return TNS_OK;
-  c->side_pending = false;
-  c->pending.clear();
-  c->side_slots = 0;
-  hipError_t e = hipEventRecord(c->ev_join, c->aux_stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
-  if (e != hipSuccess) return set_error(TNS_ERR_HIP, "backward join: %s", hipGetErrorString(e));
-  return TNS_OK;
-}
-
-// every entry point: the context exists, and earlier calls' side-stream work
-// is ordered before whatever this call enqueues
-int check_ctx(tns_ctx* c, bool join = true) {
-  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
-  return join ? join_side(c) : TNS_OK;
-}
-
-// an operand's extent: n elements every |inc| from p (empty when p is null
-// or n <= 0)
-struct Span {
-  uintptr_t lo = 0, hi = 0;
-};
-Span span(const float* p, int64_t n, int64_t inc = 1) {
-  Span s;
-  if (!p || n <= 0) return s;
-  const int64_t a = inc < 0 ? -inc : (inc == 0 ? 1 : inc);
-  s.lo = (uintptr_t)p;
-  s.hi = (uintptr_t)(p + (n - 1) * a + 1);
-  return s;
-}
 // a matrix operand of a (strided-batched) GEMM: rows x cols with leading
 // dimension ld, batch copies every stride
 Span span_mat(const float* p, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
               int64_t batch) {
   if (rows <= 0 || cols <= 0 || batch <= 0) return Span{};
   return span(p, (batch - 1) * (stride > 0 ? stride : 0) + (rows - 1) * ld + cols);
-}
-
-// every non-conv entry point: the context exists, and — during a pipelined
-// conv backward (TNS_OPT_BWD_OVERLAP = 2) — the side stream is joined only
-// when this call's operands meet a pending dW's: it writes that dW's delta
-// or input, or reads or writes its weight_updates / col workspace.  Calls
-// that touch none of them (the shortcut's addvv between two conv layers, a
-// route's copies, an upsample) leave the dW products running
-int check_ops(tns_ctx* c, std::initializer_list<Span> writes, std::initializer_list<Span> reads) {
-  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
-  if (!c->side_pending) return TNS_OK;
-  auto meet = [](const Span& a, uintptr_t lo, uintptr_t hi) {
-    return a.lo < a.hi && lo < hi && a.lo < hi && lo < a.hi;
-  };
-  for (const tns_ctx::PendingDw& d : c->pending)
-    for (int y = 0; y < 2; ++y) {
-      for (const Span& w : writes)
-        if (meet(w, d.lo[y], d.hi[y]) || meet(w, d.wlo[y], d.whi[y])) return join_side(c);
-      for (const Span& r : reads)
-        if (meet(r, d.wlo[y], d.whi[y])) return join_side(c);
-    }
-  return TNS_OK;
-}
-
-int hip_status(hipError_t e, const char* what) {
-  if (e != hipSuccess) return set_error(TNS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return TNS_OK;
-}
-
-int beta_mode_for(float beta) {
-  if (beta == 1.0f) return BETA_ONE;
-  if (beta == 0.0f && !g_strict_beta0) return BETA_ZERO;
-  return BETA_SCALE;
-}
-
-int do_gemm(tns_ctx* c, bool ta, bool tb, int64_t M, int64_t N, int64_t K, float alpha,
-            const float* A, int64_t lda, int64_t sA, const float* B, int64_t ldb, int64_t sB,
-            float beta, float* C, int64_t ldc, int64_t sC, int64_t batch, int epi,
-            const float* bias, int act, bool c_write_only = false, int variant = -1) {
-  if (M < 0 || N < 0 || K < 0 || batch < 0)
-    return set_error(TNS_ERR_ARG, "gemm: negative dimension");
-  if (M == 0 || N == 0 || batch == 0) return TNS_OK;
-  // leading dimensions, row-major (cblas_sgemm conventions)
-  const int64_t minlda = ta ? M : K, minldb = tb ? K : N;
-  if ((K > 0 && (lda < (minlda > 1 ? minlda : 1) || ldb < (minldb > 1 ? minldb : 1))) ||
-      ldc < N)
-    return set_error(TNS_ERR_ARG, "gemm: leading dimension too small (lda=%lld ldb=%lld ldc=%lld)",
-                     (long long)lda, (long long)ldb, (long long)ldc);
-  if (!C || (K > 0 && (!A || !B))) return set_error(TNS_ERR_ARG, "gemm: null operand");
-  if (epi == EPI_BIAS_ACT && (!bias || !act_supported(act)))
-    return set_error(TNS_ERR_ARG, "gemm: bad fused epilogue");
-  GemmArgs a{};
-  a.M = M; a.N = N; a.K = K;
-  a.alpha = alpha; a.beta = beta;
-  a.beta_mode = (c_write_only && beta == 0.0f) ? BETA_ZERO : beta_mode_for(beta);
-  a.A = A; a.lda = lda; a.strideA = sA;
-  a.B = B; a.ldb = ldb; a.strideB = sB;
-  a.C = C; a.ldc = ldc; a.strideC = sC;
-  a.batch = batch; a.epi = epi; a.bias = bias; a.act = act;
-  OpTimer t(c, TNS_OP_GEMM);
-  if (!ta && tb && g_nt_sdot && variant < 0 && epi == EPI_NONE)
-    return hip_status(launch_sgemm_nt_sdot(a, c->stream), "sgemm_nt launch");
-  if (ta && tb && g_tt_exact && variant < 0 && epi == EPI_NONE)
-    return hip_status(launch_sgemm_tt(a, c->stream), "sgemm_tt launch");
-  hipError_t e = launch_sgemm_variant(variant, a, ta, tb, c->stream);
-  if (e == hipErrorInvalidValue && variant >= 0)
-    return set_error(TNS_ERR_UNSUPPORTED, "gemm variant %d (%s) does not support this problem",
-                     variant, sgemm_variant_name(variant));
-  return hip_status(e, "sgemm launch");
-}
-
-ConvGeom geom(int64_t C, int64_t H, int64_t W, int64_t kH, int64_t kW, int64_t pH, int64_t pW,
-              int64_t sY, int64_t sX, int64_t dY, int64_t dX) {
-  ConvGeom g;
-  g.C = C; g.H = H; g.W = W; g.kH = kH; g.kW = kW; g.padH = pH; g.padW = pW;
-  g.sY = sY; g.sX = sX; g.dY = dY; g.dX = dX;
-  g.oh = out_dim(H, pH, kH, dY, sY);
-  g.ow = out_dim(W, pW, kW, dX, sX);
-  return g;
-}
-
-int check_geom(const ConvGeom& g) {
-  if (g.C < 0 || g.H < 0 || g.W < 0 || g.kH <= 0 || g.kW <= 0 || g.sY <= 0 || g.sX <= 0 ||
-      g.dY <= 0 || g.dX <= 0 || g.padH < 0 || g.padW < 0)
-    return set_error(TNS_ERR_ARG, "im2col: invalid geometry");
-  // kernel indexing is 32-bit inside one plane (image plane, col row) and
-  // over the col rows; offsets of planes and rows are 64-bit
-  if (g.C * g.kH * g.kW > 0x7fffffffLL || (g.oh > 0 ? g.oh : 1) * (g.ow > 0 ? g.ow : 1) >
-      0x7fffffffLL || g.H * g.W > 0x7fffffffLL)
-    return set_error(TNS_ERR_ARG, "im2col: image too large for 32-bit indexing");
-  return TNS_OK;
-}
-
-// k-table of an implicit-GEMM convolution over Hp x Wp padded images, built
-// once per geometry on the context's stream (stream order makes it visible to
-// the GEMM that follows)
-int get_ktab(tns_ctx* c, int64_t C, int64_t Hp, int64_t Wp, int64_t kH, int64_t kW, int64_t dY,
-             int64_t dX, const int** out) {
-  auto key = std::make_tuple(C, Hp, Wp, kH, kW, dY, dX);
-  auto it = c->ktabs.find(key);
-  if (it != c->ktabs.end()) {
-    *out = it->second;
-    return TNS_OK;
-  }
-  const int64_t K = C * kH * kW;
-  int* t = nullptr;
-  hipError_t e = hipMalloc(&t, (size_t)(K + KTAB_PAD) * 2 * sizeof(int));
-  if (e != hipSuccess)
-    return set_error(TNS_ERR_NOMEM, "hipMalloc(k-table) failed: %s", hipGetErrorString(e));
-  e = launch_build_ktab(t, (int)C, (int)Hp, (int)Wp, (int)kH, (int)kW, (int)dY, (int)dX,
-                        c->stream);
-  if (e != hipSuccess) {
-    hipFree(t);
-    return set_error(TNS_ERR_HIP, "k-table launch failed: %s", hipGetErrorString(e));
-  }
-  c->ktabs.emplace(key, t);
-  *out = t;
-  return TNS_OK;
 }
 
 // ---- default context for the host-pointer API (boundary A) ---------------
@@ -695,22 +365,22 @@ int tns_device_count(void) {
 int tns_set_option(int32_t opt, int64_t value) {
   switch (opt) {
     case TNS_OPT_STRICT_BETA0:
-      g_strict_beta0 = value ? 1 : 0;
+      g_opt.strict_beta0 = value ? 1 : 0;
       return TNS_OK;
     case TNS_OPT_CONV_VARIANT:
-      g_conv_variant = value < 0 ? -1 : value;
+      g_opt.conv_variant = value < 0 ? -1 : value;
       return TNS_OK;
     case TNS_OPT_CONV_PAD:
-      g_conv_pad = value < 0 ? -1 : (value ? 1 : 0);
+      g_opt.conv_pad = value < 0 ? -1 : (value ? 1 : 0);
       return TNS_OK;
     case TNS_OPT_NT_SDOT:
-      g_nt_sdot = value ? 1 : 0;
+      g_opt.nt_sdot = value ? 1 : 0;
       return TNS_OK;
     case TNS_OPT_SRSS_QUIRK:
-      g_srss_quirk = value ? 1 : 0;
+      g_opt.srss_quirk = value ? 1 : 0;
       return TNS_OK;
     case TNS_OPT_TT_EXACT:
-      g_tt_exact = value ? 1 : 0;
+      g_opt.tt_exact = value ? 1 : 0;
       return TNS_OK;
     case TNS_OPT_SDOT_FORM:
       if (value > sdot_chains_variant_count() &&
@@ -719,33 +389,33 @@ int tns_set_option(int32_t opt, int64_t value) {
       set_sdot_form((int)value);
       return TNS_OK;
     case TNS_OPT_DX_FUSED:
-      g_dx_fused = value < 0 ? 1 : (value > 2 ? 2 : value);
+      g_opt.dx_fused = value < 0 ? 1 : (value > 2 ? 2 : value);
       return TNS_OK;
     case TNS_OPT_BWD_OVERLAP:
-      g_bwd_overlap = value <= 0 ? 0 : (value >= 2 ? 2 : 1);
+      g_opt.bwd_overlap = value <= 0 ? 0 : (value >= 2 ? 2 : 1);
       return TNS_OK;
     case TNS_OPT_DW_TILE:
       if (value >= dw_tile_count()) return set_error(TNS_ERR_ARG, "no dW tile %lld", (long long)value);
-      g_dw_tile = value < -1 ? -2 : value;
+      g_opt.dw_tile = value < -1 ? -2 : value;
       return TNS_OK;
     case TNS_OPT_DX_TILE:
       if (value >= conv_tile4_ta_count()) return set_error(TNS_ERR_ARG, "no dX tile %lld", (long long)value);
-      g_dx_tile = value < -1 ? -2 : value;
+      g_opt.dx_tile = value < -1 ? -2 : value;
       return TNS_OK;
     case TNS_OPT_DW_RES:
       if (value >= dw_res_count()) return set_error(TNS_ERR_ARG, "no dW res form %lld", (long long)value);
-      g_dw_res = value < -1 ? -2 : value;
+      g_opt.dw_res = value < -1 ? -2 : value;
       return TNS_OK;
     case TNS_OPT_DERIVE_SUMS:
-      g_derive_sums = value ? 1 : 0;
+      g_opt.derive_sums = value ? 1 : 0;
       return TNS_OK;
     case TNS_OPT_SCRATCH_CAP:
-      g_scratch_cap = value > 0 ? value : 0;
+      g_opt.scratch_cap = value > 0 ? value : 0;
       return TNS_OK;
     case TNS_OPT_DX_CONV:
       if (value >= conv_tile4_dx3_count())
         return set_error(TNS_ERR_ARG, "no dX conv form %lld", (long long)value);
-      g_dx_conv = value < -1 ? -2 : value;
+      g_opt.dx_conv = value < -1 ? -2 : value;
       return TNS_OK;
     default:
       return set_error(TNS_ERR_ARG, "unknown option %d", opt);
@@ -1707,7 +1377,7 @@ int tns_hip_means_and_vars(tns_ctx* c, int64_t srcSize, int64_t dstSize, int64_t
   float* part;
   if (int r = ensure_scratch(c, SLOT_BN, 2 * groups * dstSize, &part)) return r;
   return hip_status(launch_means_vars(src + offset, groups, dstSize, bs, means, vars,
-                                      (int)g_srss_quirk, part, c->stream),
+                                      (int)g_opt.srss_quirk, part, c->stream),
                     "meansAndVars");
 }
 
@@ -1721,7 +1391,7 @@ int tns_hip_means(tns_ctx* c, int64_t srcSize, int64_t dstSize, int64_t groups,
   float* part;
   if (int r = ensure_scratch(c, SLOT_BN, 2 * groups * dstSize, &part)) return r;
   return hip_status(launch_means_vars(src + offset, groups, dstSize, bs, means, nullptr,
-                                      (int)g_srss_quirk, part, c->stream, 1),
+                                      (int)g_opt.srss_quirk, part, c->stream, 1),
                     "means");
 }
 
@@ -1736,7 +1406,7 @@ int tns_hip_variances(tns_ctx* c, int64_t srcSize, int64_t dstSize, int64_t grou
   float* part;
   if (int r = ensure_scratch(c, SLOT_BN, 2 * groups * dstSize, &part)) return r;
   return hip_status(launch_means_vars(src + offset, groups, dstSize, bs,
-                                      const_cast<float*>(means), vars, (int)g_srss_quirk, part,
+                                      const_cast<float*>(means), vars, (int)g_opt.srss_quirk, part,
                                       c->stream, 2),
                     "variances");
 }
@@ -1793,7 +1463,7 @@ int tns_hip_means_and_vars_delta(tns_ctx* c, int64_t srcSize, int64_t dstSize, i
   if (int r = ensure_scratch(c, SLOT_BN, 2 * groups * dstSize, &part)) return r;
   return hip_status(launch_mean_var_delta(delta + offset, x + offset, mean, variance, groups,
                                           dstSize, bs, mean_delta, variance_delta,
-                                          (int)g_srss_quirk, part, c->stream),
+                                          (int)g_opt.srss_quirk, part, c->stream),
                     "meansAndVarsDelta");
 }
 
@@ -1917,824 +1587,8 @@ int tns_hip_mlp_train_step(tns_ctx* c, int32_t nlayers, const int64_t* widths,
   return hip_status(launch_mlp_train_step(a, c->stream), "mlp_train_step");
 }
 
-// ---- layer drivers ------------------------------------------------------------
-int tns_hip_conv2d(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                   const float* input, const float* weights, int64_t filters, int64_t kH,
-                   int64_t kW, int64_t wPadding, int64_t hPadding, int64_t xStride,
-                   int64_t yStride, int64_t xDilation, int64_t yDilation, float* workspace,
-                   float* out) {
-  if (int r = check_ctx(c)) return r;
-  // ntensors.pas:8266-8269: negative padding => "same"-style default
-  if (wPadding < 0) wPadding = xDilation + kW / 2 - 1;
-  if (hPadding < 0) hPadding = yDilation + kH / 2 - 1;
-  // Conv2D hands (xDilation, yDilation) to im2col's (dilationY, dilationX)
-  // slots (ntensors.pas:8303); keep the swap so non-square dilation matches.
-  ConvGeom g = geom(C, H, W, kH, kW, hPadding, wPadding, yStride, xStride, xDilation, yDilation);
-  if (int r = check_geom(g)) return r;
-  // output size as the layer computes it (nConvolutionLayer.pas:92-100)
-  const int64_t oh = out_dim(H, hPadding, kH, yDilation, yStride);
-  const int64_t ow = out_dim(W, wPadding, kW, xDilation, xStride);
-  const int64_t outImg = oh * ow, kSize = kH * kW, k = C * kSize;
-  // with xDilation != yDilation the swapped im2col writes g.oh x g.ow columns
-  // per row while the col buffer and the GEMM are sized for oh x ow: the
-  // reference runs past its workspace there (or reads rows at the wrong
-  // pitch); refused before any scratch is taken or anything is launched
-  if (g.oh != oh || g.ow != ow)
-    return set_error(TNS_ERR_UNSUPPORTED,
-                     "conv2d: xDilation %lld, yDilation %lld give %lldx%lld im2col columns but "
-                     "the layer's output is %lldx%lld (ntensors.pas:8303)",
-                     (long long)xDilation, (long long)yDilation, (long long)g.oh,
-                     (long long)g.ow, (long long)oh, (long long)ow);
-  if (oh <= 0 || ow <= 0 || batch <= 0) return TNS_OK;
-  const float* Bp;
-  int64_t strideB;
-  if (kSize != 1 || xDilation * yDilation != 1 || xStride * yStride != 1) {
-    strideB = k * outImg;
-    float* ws = workspace;
-    if (!ws)
-      if (int r = ensure_scratch(c, 0, batch * strideB, &ws)) return r;
-    {
-      OpTimer t(c, TNS_OP_IM2COL);
-      if (int r = hip_status(launch_im2col(g, input, C * H * W, ws, strideB, batch, c->stream),
-                             "im2col launch"))
-        return r;
-    }
-    Bp = ws;
-  } else {
-    strideB = C * H * W;
-    Bp = input;
-  }
-  // one strided-batched launch with the weights shared (strideA = 0) — the
-  // GPU path of nConvolutionLayer.pas:1078; beta = 0 as in Conv2D (8328)
-  // The layer output is write-only here: beta = 0 does not read it (for any
-  // finite previous contents this equals the reference's 0*C up to the sign
-  // of an all-zero chain).
-  return do_gemm(c, false, false, filters, outImg, k, 1.0f, weights, k, 0, Bp, outImg, strideB,
-                 0.0f, out, outImg, outImg * filters, batch, EPI_NONE, nullptr, 0, true);
-}
-
-namespace {
-// TConvolutionalLayer.forward's Conv2D, with forwardBias + activate fused into
-// the GEMM epilogue (bias_act) or the bare convolution (the batch-norm path,
-// whose statistics need the raw output)
-int conv_forward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                      const float* input, const float* weights, const float* biases,
-                      int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
-                      int64_t dilation, int32_t activation, float* workspace, float* out,
-                      int32_t fused, bool bias_act) {
-  const int64_t oh = out_dim(H, padding, kSize, dilation, stride);
-  const int64_t ow = out_dim(W, padding, kSize, dilation, stride);
-  if (!fused) {
-    if (int r = tns_hip_conv2d(c, batch, C, H, W, input, weights, filters, kSize, kSize, padding,
-                               padding, stride, stride, dilation, dilation, workspace, out))
-      return r;
-    if (!bias_act) return TNS_OK;
-    OpTimer t(c, TNS_OP_BIAS);
-    return hip_status(launch_bias_activate(out, filters, oh * ow, biases, batch, activation,
-                                           c->stream),
-                      "bias+activate launch");
-  }
-  if (fused < TNS_CONV_UNFUSED || fused > TNS_CONV_IMPLICIT)
-    return set_error(TNS_ERR_ARG, "conv_forward: unknown schedule %d", fused);
-  ConvGeom g = geom(C, H, W, kSize, kSize, padding, padding, stride, stride, dilation, dilation);
-  if (int r = check_geom(g)) return r;
-  const int64_t outImg = oh * ow, ks = kSize * kSize, k = C * ks;
-  if (oh <= 0 || ow <= 0 || batch <= 0) return TNS_OK;
-  const bool needs_col = ks != 1 || dilation != 1 || stride != 1;
-  // logistic / tanh: bias in the GEMM epilogue (activation 4 = linear there),
-  // the transcendental activation in its own pass
-  const bool transc = act_transcendental(activation);
-  const int epi_act = transc ? 4 : activation;
-  auto activate_tail = [&]() -> int {
-    if (!bias_act || !transc) return TNS_OK;
-    OpTimer t(c, TNS_OP_ACTIVATE);
-    return hip_status(launch_activate(out, batch * filters * outImg, activation, c->stream),
-                      "activate launch");
-  };
-  // TNS_CONV_FUSED: implicit GEMM (batch folded into N: one launch with the
-  // tile shapes of pick_conv_variant, measured at or ahead of the per-image
-  // GEMM on every YOLOv3 layer, 1x1 ones included)
-  // (a padded 1x1/s1 convolution is left to the reference's direct path,
-  // which ignores the padding — ntensors.pas:8286)
-  const bool direct_ok = needs_col || padding == 0;
-  // implicit-GEMM limits (32-bit buffer offsets within one image, k-table
-  // entries, 16-bit window offsets); the library choice falls back to the
-  // im2col schedule past them
-  const int64_t img_max = C * (H + 2 * padding) * (W + 2 * padding);
-  const bool fits = !(k > 0x0fffffffLL - KTAB_PAD || img_max * 4 > 0x7fffffffLL ||
-                      (kSize - 1) * dilation >= 0x8000);
-  const bool implicit =
-      direct_ok && (fused == TNS_CONV_IMPLICIT || (fused == TNS_CONV_FUSED && fits));
-  if (implicit) {
-    // implicit GEMM: batch folded into N, B gathered from zero-padded images
-    if (!input || !weights || !out || (bias_act && !biases))
-      return set_error(TNS_ERR_ARG, "conv_forward: null operand");
-    if (g_conv_variant >= 200 && g_conv_variant < 500)
-      return set_error(TNS_ERR_UNSUPPORTED,
-                       "conv variant %lld: the ping-pong, LDS-DMA-ring and input-patch tile "
-                       "families (200..499) were removed",
-                       (long long)g_conv_variant);
-    // the implicit-GEMM operands of images b0 .. b0 + nb, gathered from stored
-    // images of Hs x Ws (img floats each): mode 1 = zero-padded copies through
-    // the k-table kt, 2 = bounds-checked against a border of pad
-    auto conv_args = [&](const float* src, int64_t img, int64_t Hs, int64_t Ws, int mode,
-                         const int* kt, int64_t pad, int64_t b0, int64_t nb) {
-      GemmArgs a{};
-      a.M = filters; a.N = nb * outImg; a.K = k;
-      a.alpha = 1.0f; a.beta = 0.0f; a.beta_mode = BETA_ZERO;
-      a.A = weights; a.lda = k; a.strideA = 0;
-      a.B = src + b0 * img; a.ldb = outImg; a.strideB = img;
-      a.C = out + b0 * outImg * filters; a.ldc = outImg; a.strideC = outImg * filters;
-      a.batch = 1; a.epi = bias_act ? EPI_BIAS_ACT : EPI_NONE; a.bias = biases;
-      a.act = epi_act;
-      a.conv = mode; a.ktab = kt; a.ktab_n = kt ? (int)(k + KTAB_PAD) : 0;
-      a.conv_H = (int)Hs; a.conv_W = (int)Ws; a.conv_ow = (int)ow; a.conv_ohw = (int)outImg;
-      a.conv_sY = (int)stride; a.conv_sX = (int)stride;
-      a.conv_pH = (int)pad; a.conv_pW = (int)pad;
-      a.conv_bytes = (int)(4 * nb * img);
-      return a;
-    };
-    // short-k first layers (3-channel 3x3): the direct kernel, one HBM pass
-    // (TNS_OPT_CONV_VARIANT >= 0 forces a GEMM tile instead)
-    if (g_conv_variant < 0 && conv_direct_applies(C, kSize, filters)) {
-      OpTimer t(c, TNS_OP_GEMM);
-      return hip_status(launch_conv_direct(input, weights, bias_act ? biases : nullptr, out, batch,
-                                           C, H, W, filters, kSize, stride, padding, dilation, oh,
-                                           ow, activation, c->stream),
-                        "direct conv launch");
-    }
-    // 1x1 / stride-1 layers straight from the input planes (conv1x1.hip)
-    // where picked, or forced by TNS_OPT_CONV_VARIANT = 600 + v
-    if (kSize == 1 && stride == 1 && padding == 0 && dilation == 1) {
-      int cv = -1;
-      if (g_conv_variant >= 600)
-        cv = (int)(g_conv_variant - 600);
-      else if (g_conv_variant < 0)
-        cv = conv1x1_pick(filters, batch * outImg, k, outImg);
-      if (cv >= 0) {
-        {
-          OpTimer t(c, TNS_OP_GEMM);
-          const hipError_t e = launch_conv1x1(cv, weights, input, bias_act ? biases : nullptr, out,
-                                              batch, filters, k, outImg, epi_act, c->stream);
-          if (e == hipErrorInvalidValue)
-            return set_error(TNS_ERR_UNSUPPORTED, "conv1x1 form %d does not fit this layer", cv);
-          if (int r = hip_status(e, "conv1x1 launch")) return r;
-        }
-        return activate_tail();
-      }
-    } else if (g_conv_variant >= 600) {
-      return set_error(TNS_ERR_UNSUPPORTED, "conv1x1 forms need a 1x1 stride-1 unpadded layer");
-    }
-    // the two-pass slab form (conv_slab.hip) where picked, or forced by
-    // TNS_OPT_CONV_VARIANT = 500 + v
-    {
-      const int64_t N = batch * outImg;
-      int sv = -1;
-      if (g_conv_variant >= 500 && g_conv_variant < 600)
-        sv = (int)(g_conv_variant - 500);
-      else if (g_conv_variant < 0 && dilation == 1)
-        sv = conv_slab_pick(filters, N, k, kSize);
-      if (sv >= 0) {
-        const int64_t need = conv_slab_floats(sv, N, k);
-        if (need < 0) return set_error(TNS_ERR_ARG, "no conv slab form %d", sv);
-        float* slab = nullptr;
-        if (int r = ensure_scratch(c, SLOT_COL, need, &slab)) return r;
-        ConvSlabArgs sa{};
-        sa.input = input; sa.weights = weights; sa.bias = bias_act ? biases : nullptr; sa.out = out;
-        sa.batch = batch; sa.C = C; sa.H = H; sa.W = W; sa.M = filters; sa.K = k; sa.ks = kSize;
-        sa.stride = stride; sa.pad = padding; sa.dil = dilation; sa.ow = ow; sa.ohw = outImg;
-        sa.act = epi_act;
-        {
-          OpTimer t(c, TNS_OP_GEMM);
-          const hipError_t e = launch_conv_slab(sv, sa, slab, c->stream);
-          if (e == hipErrorInvalidValue)
-            return set_error(TNS_ERR_UNSUPPORTED, "conv slab form %d does not fit this layer", sv);
-          if (int r = hip_status(e, "conv slab launch")) return r;
-        }
-        return activate_tail();
-      }
-    }
-    // plane-sized tiles with a bounds-checked gather from the unpadded images
-    // (conv_tile.hip) where picked, or forced by TNS_OPT_CONV_VARIANT = 100 + v
-    // (0..99: the sgemm_kernel.hpp shapes, below)
-    {
-      int tv = -1;
-      const int64_t img0 = C * H * W;
-      if ((kSize == 1 || kSize == 3) && k % 32 == 0 && img0 * 4 <= 0x7fffffffLL) {
-        if (g_conv_variant >= 100) {
-          tv = (int)(g_conv_variant - 100);
-        } else if (g_conv_variant < 0) {
-          GemmArgs probe{};
-          probe.M = filters; probe.N = batch * outImg; probe.K = k;
-          probe.conv_sY = (int)stride;
-          probe.A = weights; probe.lda = k;
-          tv = conv_tile_pick(probe, (int)kSize);
-        }
-      }
-      if (tv >= 0) {
-        const int64_t chunk = std::max<int64_t>(
-            1, std::min<int64_t>(0x7fffffffLL / (4 * img0),
-                                 0x7fffffffLL / std::max<int64_t>(outImg, 1)));
-        for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-          const int64_t nb = std::min(chunk, batch - b0);
-          const GemmArgs a = conv_args(input, img0, H, W, 2, nullptr, padding, b0, nb);
-          OpTimer t(c, TNS_OP_GEMM);
-          const hipError_t e = launch_conv_tile(tv, a, (int)kSize, (int)dilation, c->stream);
-          if (e == hipErrorInvalidValue)
-            return set_error(TNS_ERR_UNSUPPORTED, "conv tile %d does not fit this layer", tv);
-          if (int r = hip_status(e, "conv tile launch")) return r;
-        }
-        return activate_tail();
-      }
-    }
-    // Materialise the zero border (padded images, no bounds checks in the
-    // GEMM) when that copy costs under ~5% of the GEMM: copy time
-    // ~bytes/4 TB/s vs GEMM ~flops/80 TF/s.
-    const double flops = 2.0 * (double)filters * (double)(batch * outImg) * (double)k;
-    const int64_t Hpad = H + 2 * padding, Wpad = W + 2 * padding;
-    const bool padded = padding == 0 ||
-                        (g_conv_pad < 0 ? 8.0 * (double)(batch * C * Hpad * Wpad) * 400.0 < flops
-                                        : g_conv_pad == 1);
-    const int64_t Hs = padded ? Hpad : H, Ws = padded ? Wpad : W, img = C * Hs * Ws;
-    // (k-table: 8-byte entries in one buffer resource, window offsets packed
-    // in 16 bits)
-    if (k > 0x0fffffffLL - KTAB_PAD || img * 4 > 0x7fffffffLL || (kSize - 1) * dilation >= 0x8000)
-      return set_error(TNS_ERR_ARG, "conv_forward: image too large for the implicit GEMM");
-    const int* kt = nullptr;
-    if (int r = get_ktab(c, C, Hs, Ws, kSize, kSize, dilation, dilation, &kt)) return r;
-    const float* src = input;
-    if (padded && padding > 0) {
-      float* pbuf = nullptr;
-      if (int r = ensure_scratch(c, 1, batch * img, &pbuf)) return r;
-      OpTimer t(c, TNS_OP_IM2COL);
-      if (int r = hip_status(launch_pad_images(input, batch, C, H, W, padding, padding, pbuf,
-                                               c->stream), "pad launch"))
-        return r;
-      src = pbuf;
-    }
-    // buffer offsets are 32-bit: images per launch such that the B extent
-    // stays below 2^31 bytes (and N below 2^31)
-    const int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>(0x7fffffffLL / (4 * img), 0x7fffffffLL / std::max<int64_t>(outImg, 1)));
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-      const int64_t nb = std::min(chunk, batch - b0);
-      const GemmArgs a =
-          conv_args(src, img, Hs, Ws, padded ? 1 : 2, kt, padded ? 0 : padding, b0, nb);
-      OpTimer t(c, TNS_OP_GEMM);
-      // (99: the sgemm_kernel.hpp shape heuristic, bypassing conv_tile)
-      hipError_t e = launch_sgemm_conv_variant(g_conv_variant == 99 ? -1 : (int)g_conv_variant,
-                                               a, c->stream);
-      if (e == hipErrorInvalidValue)
-        return set_error(TNS_ERR_UNSUPPORTED, "conv variant %lld unsupported",
-                         (long long)g_conv_variant);
-      if (int r = hip_status(e, "implicit conv launch")) return r;
-    }
-    return activate_tail();
-  }
-  const float* Bp;
-  int64_t strideB;
-  if (needs_col) {
-    strideB = k * outImg;
-    float* ws = workspace;
-    if (!ws)
-      if (int r = ensure_scratch(c, 0, batch * strideB, &ws)) return r;
-    {
-      OpTimer t(c, TNS_OP_IM2COL);
-      if (int r = hip_status(launch_im2col(g, input, C * H * W, ws, strideB, batch, c->stream),
-                             "im2col launch"))
-        return r;
-    }
-    Bp = ws;
-  } else {
-    strideB = C * H * W;
-    Bp = input;
-  }
-  // conv GEMM with forwardBias + activate fused into the epilogue
-  if (int r = do_gemm(c, false, false, filters, outImg, k, 1.0f, weights, k, 0, Bp, outImg,
-                      strideB, 0.0f, out, outImg, outImg * filters, batch,
-                      bias_act ? EPI_BIAS_ACT : EPI_NONE, biases, epi_act, true))
-    return r;
-  return activate_tail();
-}
-}  // namespace
-
-int tns_hip_conv_forward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                         const float* input, const float* weights, const float* biases,
-                         int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
-                         int64_t dilation, int32_t activation, float* workspace, float* out,
-                         int32_t fused) {
-  if (int r = check_ctx(c)) return r;
-  if (!act_supported(activation))
-    return set_error(TNS_ERR_UNSUPPORTED, "activation %d not implemented", activation);
-  return conv_forward_impl(c, batch, C, H, W, input, weights, biases, filters, kSize, stride,
-                           padding, dilation, activation, workspace, out, fused, true);
-}
-
-int tns_hip_conv_forward_train(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                               const float* input, const float* weights, int64_t filters,
-                               int64_t kSize, int64_t stride, int64_t padding, int64_t dilation,
-                               int32_t activation, const float* scales, const float* biases,
-                               float* rolling_mean, float* rolling_variance, float bnMomentum,
-                               int32_t training, float* mean, float* variance, float* x,
-                               float* x_norm, float* workspace, float* out) {
-  if (int r = check_ctx(c)) return r;
-  if (!act_supported(activation))
-    return set_error(TNS_ERR_UNSUPPORTED, "activation %d not implemented", activation);
-  if (!scales || !biases || !rolling_mean || !rolling_variance || !out ||
-      (training && (!mean || !variance || !x || !x_norm)))
-    return set_error(TNS_ERR_ARG, "conv_forward_train: null operand");
-  const int64_t oh = out_dim(H, padding, kSize, dilation, stride);
-  const int64_t ow = out_dim(W, padding, kSize, dilation, stride);
-  if (oh <= 0 || ow <= 0 || batch <= 0 || filters <= 0) return TNS_OK;
-  const int64_t bs = oh * ow;
-  // state.input.Conv2D(weights, output, ...) (nConvolutionLayer.pas:508)
-  if (int r = conv_forward_impl(c, batch, C, H, W, input, weights, nullptr, filters, kSize,
-                                stride, padding, dilation, activation, workspace, out,
-                                TNS_CONV_FUSED, false))
-    return r;
-  OpTimer t(c, TNS_OP_BIAS);
-  if (!training)  // blockNormalize with the rolling statistics, scale, bias, activate
-    return hip_status(launch_bn_apply(out, nullptr, nullptr, out, batch, filters, bs,
-                                      rolling_mean, rolling_variance, scales, biases, activation,
-                                      c->stream),
-                      "batchNorm launch");
-  float* part;
-  if (int r = ensure_scratch(c, SLOT_BN, 2 * batch * filters, &part)) return r;
-  if (int r = hip_status(launch_means_vars(out, batch, filters, bs, mean, variance,
-                                           (int)g_srss_quirk, part, c->stream),
-                         "meansAndVars launch"))
-    return r;
-  if (int r = hip_status(launch_rolling_update(filters, rolling_mean, rolling_variance, mean,
-                                               variance, bnMomentum, c->stream),
-                         "rolling update launch"))
-    return r;
-  return hip_status(launch_bn_apply(out, x, x_norm, out, batch, filters, bs, mean, variance,
-                                    scales, biases, activation, c->stream),
-                    "batchNorm launch");
-}
-
-namespace {
-struct ConvBN {  // batchNormBack operands (nbaselayer.pas:372-395); scales == nullptr: none
-  const float *scales, *x, *x_norm, *mean, *variance;
-  float *scale_updates, *mean_delta, *variance_delta;
-};
-
-int conv_backward_impl(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                       const float* input, const float* weights, int64_t filters, int64_t kSize,
-                       int64_t stride, int64_t padding, int64_t dilation, int32_t activation,
-                       const float* output, float* delta, float* bias_updates,
-                       float* weight_updates, float* workspace, float* state_delta,
-                       const ConvBN& bn) {
-  // (pipelined mode: this call's dW queues behind the pending ones on the
-  // side stream; its other work touches none of their operands)
-  if (!c) return check_ctx(c);
-  bool pipe = g_bwd_overlap == 2 && !c->telemetry && ensure_side_stream(c);
-  if (int r = check_ctx(c, !pipe)) return r;
-  if (!act_supported(activation))
-    return set_error(TNS_ERR_UNSUPPORTED, "activation %d not implemented", activation);
-  // delta / output are [batch][filters][outH*outW] with the layer's outH =
-  // (h + 2p - k) div s + 1 (nConvolutionLayer.pas:92-100); the backward
-  // im2col / col2im pad with padding*dilation (640, 665), which yields those
-  // columns for the "same" paddings at any dilation — other geometries make
-  // the reference read past its workspace and are refused
-  ConvGeom g = geom(C, H, W, kSize, kSize, padding * dilation, padding * dilation, stride, stride,
-                    dilation, dilation);
-  if (int r = check_geom(g)) return r;
-  if (g.oh != (H + 2 * padding - kSize) / stride + 1 ||
-      g.ow != (W + 2 * padding - kSize) / stride + 1)
-    return set_error(TNS_ERR_UNSUPPORTED,
-                     "conv_backward: dilation %lld with padding %lld gives %lldx%lld im2col "
-                     "columns but the layer's output is %lldx%lld (nConvolutionLayer.pas:92-100, "
-                     "640)",
-                     (long long)dilation, (long long)padding, (long long)g.oh, (long long)g.ow,
-                     (long long)((H + 2 * padding - kSize) / stride + 1),
-                     (long long)((W + 2 * padding - kSize) / stride + 1));
-  const int64_t i_m = filters, i_n = kSize * kSize * C, i_k = g.oh * g.ow;
-  const int64_t colSize = i_n * i_k;
-  if (batch <= 0 || i_k <= 0 || filters <= 0) return TNS_OK;
-  if (!input || !weights || !output || !delta || !weight_updates || (!bn.scales && !bias_updates))
-    return set_error(TNS_ERR_ARG, "conv_backward: null operand");
-  if (bn.scales && (!bn.x || !bn.x_norm || !bn.mean || !bn.variance || !bn.scale_updates ||
-                    !bn.mean_delta || !bn.variance_delta))
-    return set_error(TNS_ERR_ARG, "conv_backward: null batch-norm operand");
-  if (pipe) {
-    // this call writes delta (in place) and state.delta on the context's
-    // stream: if a pending dW reads either (an earlier call on the same
-    // layers, e.g. the previous pass), the side stream is joined first (no
-    // per-call event: the join is only paid where the ranges meet)
-    // (the same test as every other entry point's, over this call's
-    // context-stream operands; its own dW queues on the side stream)
-    const int64_t nf = bn.scales ? filters : 0;
-    if (int r = check_ops(c,
-                          {span(delta, batch * filters * i_k), span(state_delta, batch * C * H * W),
-                           span(bias_updates, bn.scales ? 0 : filters), span(bn.scale_updates, nf),
-                           span(bn.mean_delta, nf), span(bn.variance_delta, nf)},
-                          {span(output, batch * filters * i_k), span(weights, filters * i_n),
-                           span(bn.x, nf ? batch * filters * i_k : 0),
-                           span(bn.x_norm, nf ? batch * filters * i_k : 0),
-                           span(bn.scales, nf), span(bn.mean, nf), span(bn.variance, nf)}))
-      return r;
-  }
-  float* part;
-  if (int r = ensure_scratch(c, SLOT_BN, 3 * batch * filters, &part)) return r;
-  // batchNormBack's five passes as one chain pass over delta, output, x_norm
-  // and x (the three reductions) + normalizeDelta deriving and scaling each
-  // term as it loads it, where the chain kernels apply
-  hipError_t fe = hipErrorNotSupported;
-  if (bn.scales && g_bn_fused)
-    fe = launch_bn_backward_fused(bn.scale_updates, bn.x_norm, delta, output, activation, bn.x,
-                                  bn.mean, bn.variance, bn.scales, bn.mean_delta,
-                                  bn.variance_delta, batch, filters, i_k, (int)g_srss_quirk, part,
-                                  c->stream);
-  if (fe != hipErrorNotSupported) {
-    if (int r = hip_status(fe, "batchNormBack launch")) return r;
-  } else if (bn.scales) {
-    // Derivative(): delta *= f'(output), then batchNormBack:
-    // scale_updates.addDots(x_norm, delta); delta.forwardScale(scales);
-    // MeansAndVarsDelta; normalizeDelta — and no bias_updates term
-    // (nConvolutionLayer.pas:601-604).  Three passes instead of five: the
-    // derive rides addDots' loads (each derived term written back), and the
-    // scale is applied to each delta term as MeansAndVarsDelta and
-    // normalizeDelta load it (the same one rounding forwardScale would store)
-    if (int r = hip_status(launch_add_dots_derive(bn.scale_updates, bn.x_norm, delta, output,
-                                                  activation, batch, filters, i_k, part,
-                                                  c->stream),
-                           "derive + addDots launch"))
-      return r;
-    const float* fold = bn_folds_scale(i_k) ? bn.scales : nullptr;
-    if (!fold)
-      if (int r = hip_status(launch_scale_add(delta, batch, filters, i_k, bn.scales, nullptr, 1,
-                                              c->stream), "forwardScale launch"))
-        return r;
-    if (int r = hip_status(launch_mean_var_delta(delta, bn.x, bn.mean, bn.variance, batch, filters,
-                                                 i_k, bn.mean_delta, bn.variance_delta,
-                                                 (int)g_srss_quirk, part, c->stream, fold),
-                           "meansAndVarsDelta launch"))
-      return r;
-    if (int r = hip_status(launch_normalize_delta(bn.x, bn.mean, bn.variance, bn.mean_delta,
-                                                  bn.variance_delta, delta, batch, filters, i_k,
-                                                  c->stream, fold), "normalizeDelta launch"))
-      return r;
-  } else {
-    // Derivative(): delta *= f'(output), then bias_updates.addSums(delta) —
-    // one pass (each derived term written back as it enters the sums' chains)
-    if (g_derive_sums) {
-      if (int r = hip_status(launch_derive_add_sums(bias_updates, delta, output, activation, batch,
-                                                    filters, i_k, part, c->stream),
-                             "derive + addSums launch"))
-        return r;
-    } else {
-      if (int r = hip_status(launch_derive(output, batch * filters * i_k, activation, delta,
-                                           c->stream), "derive launch"))
-        return r;
-      if (int r = hip_status(launch_add_sums(bias_updates, delta, batch, filters, i_k, part,
-                                             c->stream), "addSums launch"))
-        return r;
-    }
-  }
-  // state.input.im2Col(...) — a 1x1/s1/p0 col matrix is the input itself
-  const bool needs_col = kSize != 1 || stride != 1 || padding != 0 || dilation != 1;
-  // state.delta of stride-1 layers without the col matrix (conv_dx.hip)
-  // state.delta of a 1x1 / stride-1 layer as a 1x1 convolution of the delta
-  // planes with W^T on conv1x1.hip, the col2im add in its epilogue (the same
-  // chains and the same add as the TN product with EPI_ADD)
-  const int dx1 = state_delta && g_dx_c1 && g_dx_fused != 2 && kSize == 1 && stride == 1 &&
-                          padding == 0 && dilation == 1
-                      ? conv1x1_pick(C, batch * i_k, filters, i_k)
-                      : -1;
-  const bool fused_dx =
-      dx1 < 0 && state_delta && dilation == 1 &&
-      ((g_dx_fused == 1 && conv_dx_fused_applies(C, H, W, kSize, stride, filters, g.oh, g.ow)) ||
-       (g_dx_fused == 2 && conv_dx_fused_fits(C, H, W, stride, filters, g.oh, g.ow)));
-  // dW with the im2col matrix generated inside the sdot-order product
-  // (dw_tile.hip): no col matrix, no im2col pass
-  DwArgs da{};
-  int dwv = -1;
-  if (g_nt_sdot && g_dw_tile != -2 && (kSize == 1 || kSize == 3) &&
-      C * H * W < (1LL << 27) && i_n <= 0x7fffffffLL && i_k <= 0x7fffffffLL && batch <= 65535) {
-    da.delta = delta; da.x = input; da.part = nullptr;
-    da.M = (int)i_m; da.N = (int)i_n; da.HW = (int)i_k;
-    da.C = (int)C; da.H = (int)H; da.W = (int)W; da.oW = (int)g.ow;
-    da.stride = (int)stride; da.pad = (int)(padding * dilation); da.dil = (int)dilation;
-    da.va = i_k % 4 == 0 && (reinterpret_cast<uintptr_t>(delta) & 15) == 0;
-    da.alpha = 1.0f;
-    da.strideA = i_m * i_k; da.strideX = C * H * W; da.strideP = i_m * i_n; da.batch = batch;
-    dwv = g_dw_tile >= 0 ? (int)g_dw_tile : dw_tile_pick(da, (int)kSize);
-  }
-  // dW as residue chains in sequence over residue-major copies of delta and
-  // the im2col matrix (dw_res.hip): the 3x3 layers with large outputs
-  int dwr = -1;
-  if (g_nt_sdot && g_dw_res != -2 && g_dw_tile < 0 && batch <= 65535 && i_k >= 64) {
-    if (g_dw_res >= 0)
-      dwr = (int)g_dw_res;
-    else if (kSize == 3)  // (1x1 layers: behind the sdot kernels, 0.048 -> 0.058 ms at 52^2)
-      dwr = dw_res_pick(i_m, i_n, i_k, batch);
-  }
-  // its scratch (residue-major copies, group planes: in addition to the
-  // caller's workspace), sized before any fork; when the form was picked by
-  // shape and that memory cannot be had, the dW falls back to the paths
-  // that need only the workspace (dw_tile, or im2col + the sdot kernels)
-  DwResArgs dres{};
-  if (dwr >= 0) {
-    const int64_t rowlen = 8 * dw_res_k4(i_k);
-    int r = ensure_scratch(c, SLOT_RES_A, batch * i_m * rowlen + 32, &dres.dA, pipe);
-    if (!r)
-      r = ensure_scratch(c, SLOT_RES_B, batch * dw_res_b_rows(dwr, i_n) * rowlen + 32, &dres.dB,
-                         pipe);
-    if (!r) r = ensure_scratch(c, SLOT_DW, batch * dw_res_groups(dwr) * i_m * i_n, &dres.part, pipe);
-    if (r) {
-      if (g_dw_res >= 0) return r;  // (forced: the error stands)
-      tns_clear_error();
-      release_scratch(c, SLOT_RES_A);
-      release_scratch(c, SLOT_RES_B);
-      dwr = -1;
-    }
-  }
-  if (dwr >= 0) dwv = -1;
-  // a 1x1/s1/p0 layer's col2im adds each col element to its own pixel once:
-  // the dX product adds into state.delta in its epilogue instead (EPI_ADD,
-  // the same add), no col matrix
-  const bool dx_direct = state_delta && !needs_col && !fused_dx;
-  // state.delta of a stride-1 3x3 layer as one implicit transposed
-  // convolution (conv_tile4 DX forms: each tap's filter chain added to the
-  // pixel in scol2im's order), no col matrix
-  // (stride 2: four such convolutions, one per output pixel parity class,
-  // each over the taps col2im adds to that class)
-  int dxc = -1;
-  const bool dxc_s2 = stride == 2;
-  if (state_delta && !fused_dx && kSize == 3 && (stride == 1 || stride == 2) && dilation == 1 &&
-      g_dx_conv != -2)
-    dxc = g_dx_conv >= 0 ? (int)g_dx_conv
-          : dxc_s2   ? conv_tile4_dx3s2_pick(batch, C, H, W, filters, kSize, padding)
-                     : conv_tile4_dx3_pick(batch, C, H, W, filters, kSize, padding);
-  // dW (im2col + sdot or dw_tile, accumulate) and state.delta (TN + col2im
-  // or the fused kernel) read delta and write disjoint outputs: with a
-  // state.delta they run concurrently, state.delta's chain on the context's
-  // side stream (fork / join events), each with its own col buffer —
-  // nothing changes in either result.  Telemetry times ops one by one, so it
-  // keeps them in sequence.
-  bool overlap = !pipe && state_delta && g_bwd_overlap && !c->telemetry && ensure_side_stream(c);
-  const bool dw_col = needs_col && dwv < 0 && dwr < 0;  // dW reads an im2col matrix
-  // state.delta's own col buffer when both chains need one at once (the
-  // overlap's extra memory, tns.h); if it cannot be had, the sequential
-  // schedule shares the one col buffer instead
-  float* dx_ws = nullptr;
-  const bool dx_col = state_delta && !fused_dx && !dx_direct && dxc < 0;  // dX writes a col matrix
-  if (overlap && dw_col && dx_col && ensure_scratch(c, SLOT_COL_DX, batch * colSize, &dx_ws)) {
-    tns_clear_error();
-    overlap = false;
-  }
-  // (pipelined: state.delta's chain always has its own col buffer — the
-  // pending dW products may still read the shared one)
-  // (if that buffer cannot be had: the pending dW joined, this call in
-  // sequence within the caller's workspace)
-  if (pipe && dx_col && ensure_scratch(c, SLOT_COL_DX, batch * colSize, &dx_ws)) {
-    tns_clear_error();
-    dx_ws = nullptr;
-    pipe = false;
-    if (int r = join_side(c)) return r;
-  }
-  float* ws = workspace;
-  if (!ws && (dw_col || (dx_col && !dx_ws && !(overlap && dw_col))))
-    if (int r = ensure_scratch(c, SLOT_COL, batch * colSize, &ws, pipe)) return r;
-  if (!dx_ws) dx_ws = ws;  // col buffer of state.delta's chain
-  // scratch of the fused state.delta kernel, sized before any fork (a growth
-  // inside the side-stream chain would free a buffer the main stream may use)
-  float* wt = nullptr;
-  if (fused_dx || dxc >= 0 || dx1 >= 0)
-    if (int r = ensure_scratch(c, SLOT_WT, filters * C * kSize * kSize, &wt)) return r;
-
-  auto run_dw = [&]() -> int {
-    const float* col = input;
-    if (dwr >= 0) {
-      DwResArgs d = dres;  // (scratch sized above)
-      d.g = g;
-      d.x = input; d.xStride = C * H * W;
-      d.delta = delta; d.weight_updates = weight_updates;
-      d.M = i_m; d.N = i_n; d.K = i_k; d.batch = batch;
-      d.direct = !needs_col; d.alpha = 1.0f;
-      OpTimer t(c, TNS_OP_GEMM);
-      const hipError_t e = launch_dw_res(dwr, d, c->stream);
-      if (e == hipErrorInvalidValue)
-        return set_error(TNS_ERR_UNSUPPORTED, "dW res form %d does not fit this layer", dwr);
-      return hip_status(e, "dW res launch");
-    }
-    if (dwv >= 0) {
-      float* part = nullptr;
-      if (int r = ensure_scratch(c, SLOT_DW, batch * i_m * i_n, &part, pipe)) return r;
-      da.part = part;
-      {
-        OpTimer t(c, TNS_OP_GEMM);
-        const hipError_t e = launch_dw_tile(dwv, da, (int)kSize, c->stream);
-        if (e == hipErrorInvalidValue)
-          return set_error(TNS_ERR_UNSUPPORTED, "dW tile %d does not fit this layer", dwv);
-        if (int r = hip_status(e, "dW tile launch")) return r;
-      }
-      return hip_status(launch_add_in_order(weight_updates, part, i_m * i_n, batch, c->stream),
-                        "dW accumulate launch");
-    }
-    if (needs_col) {
-      OpTimer t(c, TNS_OP_IM2COL);
-      if (int r = hip_status(launch_im2col(g, input, C * H * W, ws, colSize, batch, c->stream),
-                             "im2col launch"))
-        return r;
-      col = ws;
-    }
-    // weight_updates += delta_b . col_b^T, one NT GEMM per image (beta = 1),
-    // in image order as the reference loop (nConvolutionLayer.pas:636-640):
-    // each image adds sum_b = 1*sdot(...) to C.  The sums of different images
-    // are independent, so they are computed by ONE strided-batched sdot launch
-    // (each stored as is, BETA_STORE), then added to C image by image in the
-    // reference's order — the same roundings, batch-fold more parallelism for
-    // the few-tile, long-k dW shapes.
-    if (g_nt_sdot && batch > 1) {
-      float* part = nullptr;
-      if (int r = ensure_scratch(c, SLOT_DW, batch * i_m * i_n, &part, pipe)) return r;
-      GemmArgs a{};
-      a.M = i_m; a.N = i_n; a.K = i_k;
-      a.alpha = 1.0f; a.beta = 0.0f; a.beta_mode = BETA_STORE;
-      a.A = delta; a.lda = i_k; a.strideA = i_m * i_k;
-      a.B = col; a.ldb = i_k; a.strideB = colSize;
-      a.C = part; a.ldc = i_n; a.strideC = i_m * i_n;
-      a.batch = batch; a.epi = EPI_NONE;
-      {
-        OpTimer t(c, TNS_OP_GEMM);
-        if (int r = hip_status(launch_sgemm_nt_sdot(a, c->stream), "sgemm_nt launch")) return r;
-      }
-      return hip_status(launch_add_in_order(weight_updates, part, i_m * i_n, batch, c->stream),
-                        "dW accumulate launch");
-    }
-    for (int64_t b = 0; b < batch; ++b)
-      if (int r = do_gemm(c, false, true, i_m, i_n, i_k, 1.0f, delta + b * i_m * i_k, i_k, 0,
-                          col + b * colSize, i_k, 0, 1.0f, weight_updates, i_n, 0, 1, EPI_NONE,
-                          nullptr, 0))
-        return r;
-    return TNS_OK;
-  };
-
-  auto run_dx = [&]() -> int {
-    if (fused_dx) {
-      // per image pixel: each window tap's ascending-f chain, added to the
-      // pixel in (kr, kc) order for the taps scol2im does not skip — the same
-      // roundings as the two stages below (646-660)
-      OpTimer t(c, TNS_OP_GEMM);
-      return hip_status(launch_conv_dx_col2im(weights, wt, delta, state_delta, batch, C, H, W,
-                                              filters, kSize, padding, dilation, g.oh, g.ow,
-                                              c->stream),
-                        "fused dX + col2im launch");
-    }
-    // col_b = W^T . delta_b (TN strided batched, weights shared, beta = 0 into
-    // the workspace), then col2im accumulates into state.delta (646-660).  All
-    // images in one launch on conv_tile4's k-major-A forms where they apply (a
-    // 1x1 "convolution" over the delta planes, the same chains), else the TN
-    // GEMM
-    if (dxc >= 0) {
-      OpTimer t(c, TNS_OP_GEMM);
-      if (int r = hip_status(
-              dxc_s2 ? launch_transpose_taps(weights, wt, filters, C, kSize * kSize, c->stream,
-                                             conv_tile4_dx3s2_order(padding))
-                     : launch_transpose_taps(weights, wt, filters, C, kSize * kSize, c->stream),
-              "weights transpose launch"))
-        return r;
-      const hipError_t e =
-          dxc_s2 ? launch_conv_tile4_dx3s2(dxc, wt, delta, state_delta, batch, C, H, W, filters,
-                                           padding, g.oh, g.ow, c->stream)
-                 : launch_conv_tile4_dx3(dxc, wt, delta, state_delta, batch, C, H, W, filters,
-                                         kSize, padding, g.oh, g.ow, c->stream);
-      if (e != hipErrorInvalidValue) return hip_status(e, "dX conv launch");
-      return set_error(TNS_ERR_UNSUPPORTED, "dX conv form %d does not fit this layer", dxc);
-    }
-    bool done = false;
-    float* col = dx_direct ? state_delta : dx_ws;
-    if (dx1 >= 0) {  // (1x1 / stride 1: dx_direct)
-      OpTimer t(c, TNS_OP_GEMM);
-      if (int r = hip_status(launch_transpose(weights, wt, filters, C, c->stream),
-                             "weights transpose launch"))
-        return r;
-      const hipError_t e = launch_conv1x1(dx1, wt, delta, nullptr, state_delta, batch, C, filters,
-                                          i_k, 0, c->stream, true);
-      if (e == hipSuccess) return TNS_OK;
-      if (e != hipErrorInvalidValue) return hip_status(e, "dX 1x1 launch");
-      // (operands off the 16-byte alignment the DMA needs: the TN product)
-    }
-    if (g_dx_tile != -2) {
-      const int dv = g_dx_tile >= 0 ? (int)g_dx_tile : conv_tile4_dx_pick(i_n, batch * i_k, i_m, kSize);
-      if (dv >= 0) {
-        OpTimer t(c, TNS_OP_GEMM);
-        const hipError_t e = launch_conv_tile4_dx(dv, weights, delta, col, batch, C, kSize,
-                                                  filters, g.oh, g.ow, c->stream, dx_direct);
-        if (e == hipSuccess)
-          done = true;
-        else if (e != hipErrorInvalidValue || g_dx_tile >= 0)
-          return e == hipErrorInvalidValue
-                     ? set_error(TNS_ERR_UNSUPPORTED, "dX tile %d does not fit this layer", dv)
-                     : hip_status(e, "dX tile launch");
-      }
-    }
-    if (!done)
-      if (int r = do_gemm(c, true, false, i_n, i_k, i_m, 1.0f, weights, i_n, 0, delta, i_k,
-                          i_m * i_k, 0.0f, col, i_k, colSize, batch,
-                          dx_direct ? EPI_ADD : EPI_NONE, nullptr, 0, true))
-        return r;
-    if (dx_direct) return TNS_OK;
-    OpTimer t(c, TNS_OP_COL2IM);
-    return hip_status(launch_col2im(g, dx_ws, colSize, state_delta, C * H * W, batch, c->stream),
-                      "col2im launch");
-  };
-
-  if (pipe) {
-    // dW enqueued on the side stream behind the earlier calls' (fork: after
-    // this call's derive / bias sums), state.delta's chain on the context's
-    // stream; no join — the side stream's work is joined by the next call of
-    // any other entry point (tns.h TNS_OPT_BWD_OVERLAP)
-    TNS_HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    TNS_HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-    hipStream_t main = c->stream;
-    c->home_stream = main;
-    c->stream = c->aux_stream;
-    const int rw = run_dw();
-    c->stream = main;
-    c->home_stream = nullptr;
-    c->side_pending = true;
-    // the record of this dW's operands and of the scratch slots it uses
-    // (kept after a failed launch too: whatever it enqueued stays ordered)
-    tns_ctx::PendingDw d;
-    const Span rd = span(delta, batch * filters * i_k), ri = span(input, batch * C * H * W);
-    const Span wu = span(weight_updates, i_m * i_n);
-    const Span wc = dw_col && ws == workspace ? span(ws, batch * colSize) : Span{};
-    d.lo[0] = rd.lo; d.hi[0] = rd.hi;
-    d.lo[1] = ri.lo; d.hi[1] = ri.hi;
-    d.wlo[0] = wu.lo; d.whi[0] = wu.hi;
-    d.wlo[1] = wc.lo; d.whi[1] = wc.hi;
-    c->pending.push_back(d);
-    c->side_slots |= 1u << SLOT_RES_A | 1u << SLOT_RES_B | 1u << SLOT_DW |
-                     (dw_col && ws != workspace ? 1u << SLOT_COL : 0u);
-    if (rw) return rw;
-    return state_delta ? run_dx() : TNS_OK;
-  }
-  if (!overlap) {
-    if (int r = run_dw()) return r;
-    return state_delta ? run_dx() : TNS_OK;
-  }
-  TNS_HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-  TNS_HIP_TRY(hipStreamWaitEvent(c->ovl_stream, c->ev_fork, 0));
-  int rx;
-  {
-    // state.delta's chain enqueued on the overlap stream (every launch inside
-    // run_dx goes to c->stream), the context's stream restored after
-    hipStream_t main = c->stream;
-    c->stream = c->ovl_stream;
-    rx = run_dx();
-    c->stream = main;
-  }
-  // joined even after an error, so later work on the stream stays ordered
-  const hipError_t ej = hipEventRecord(c->ev_join, c->ovl_stream);
-  const int rw = run_dw();
-  const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(c->stream, c->ev_join, 0) : ej;
-  if (rx) return rx;
-  if (rw) return rw;
-  return hip_status(ew, "backward join");
-}
-}  // namespace
-
-int tns_hip_conv_backward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                          const float* input, const float* weights, int64_t filters,
-                          int64_t kSize, int64_t stride, int64_t padding, int64_t dilation,
-                          int32_t activation, const float* output, float* delta,
-                          float* bias_updates, float* weight_updates, float* workspace,
-                          float* state_delta) {
-  return conv_backward_impl(c, batch, C, H, W, input, weights, filters, kSize, stride, padding,
-                            dilation, activation, output, delta, bias_updates, weight_updates,
-                            workspace, state_delta, ConvBN{});
-}
-
-int tns_hip_conv_backward_bn(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
-                             const float* input, const float* weights, int64_t filters,
-                             int64_t kSize, int64_t stride, int64_t padding, int64_t dilation,
-                             int32_t activation, const float* output, float* delta,
-                             const float* scales, const float* x, const float* x_norm,
-                             const float* mean, const float* variance, float* scale_updates,
-                             float* mean_delta, float* variance_delta, float* weight_updates,
-                             float* workspace, float* state_delta) {
-  if (!scales) return set_error(TNS_ERR_ARG, "conv_backward_bn: null scales");
-  ConvBN bn{scales, x, x_norm, mean, variance, scale_updates, mean_delta, variance_delta};
-  return conv_backward_impl(c, batch, C, H, W, input, weights, filters, kSize, stride, padding,
-                            dilation, activation, output, delta, nullptr, weight_updates,
-                            workspace, state_delta, bn);
-}
-
 int tns_gemm_variant_count(void) { return sgemm_variant_count(); }
 int tns_sdot_chains_variant_count(void) { return sdot_chains_variant_count(); }
-int tns_conv_tile_variant_count(void) { return conv_tile_count(); }
-int tns_conv_slab_count(void) { return conv_slab_count(); }
-int tns_conv1x1_count(void) { return conv1x1_count(); }
-const char* tns_conv1x1_name(int32_t v) { return conv1x1_name(v); }
-const char* tns_conv_slab_name(int32_t v) { return conv_slab_name(v); }
-int tns_conv_dx_tile_count(void) { return conv_tile4_ta_count(); }
-int tns_conv_dx_conv_count(void) { return conv_tile4_dx3_count(); }
-int tns_conv_dw_res_count(void) { return dw_res_count(); }
-int tns_conv_dw_tile_count(void) { return dw_tile_count(); }
-const char* tns_conv_tile_variant_name(int32_t v) { return conv_tile_name(v); }
 const char* tns_sdot_chains_variant_name(int32_t v) { return sdot_chains_variant_name(v); }
 int tns_sdot_rc_variant_count(void) { return sdot_rc_variant_count(); }
 const char* tns_sdot_rc_variant_name(int32_t v) { return sdot_rc_variant_name(v); }

@@ -467,4 +467,103 @@ struct MlpArgs {
 int64_t mlp_buffer_floats(int nlayers, const int64_t* widths, int bn, int64_t batch);
 hipError_t launch_mlp_train_step(const MlpArgs& a, hipStream_t s);
 
+// ---- conv dispatch (conv_api.cpp) --------------------------------------------
+// Which kernels a convolutional layer's forward and backward run on is decided
+// by two pure functions of the layer's shape and the options: no context, no
+// HIP call, no allocation, no global.  The executors read the plan and nothing
+// else; what only the context knows (scratch refused, no side stream,
+// telemetry on, a launch refusing misaligned operands) stays with them.
+struct Options;  // tns_ctx.hpp
+struct ConvShape {
+  int64_t batch, C, H, W, filters, kSize, stride, padding, dilation;
+  int32_t activation;
+  // forward only: the weight rows are float4-loadable (conv_tile_pick asks)
+  bool weights_aligned16;
+};
+constexpr int kPlanMsg = 256;
+
+enum ConvFwdPath {
+  FWD_EMPTY = 0,  // no output element: nothing runs
+  FWD_UNFUSED,    // tns_hip_conv2d + the bias / activation pass
+  FWD_IM2COL,     // im2col (or the input itself) + GEMM with the fused epilogue
+  FWD_DIRECT,     // conv_direct.hip
+  FWD_CONV1X1,    // conv1x1.hip
+  FWD_SLAB,       // conv_slab.hip
+  FWD_TILE,       // conv_tile.hip / conv_tile4.hip plane tiles
+  FWD_IMPLICIT    // sgemm_kernel.hpp tiles over a k-table
+};
+struct ConvFwdPlan {
+  int err = 0;  // TNS_ERR_* and its message where the call is refused
+  char msg[kPlanMsg] = {};
+  ConvShape s{};
+  int64_t oh = 0, ow = 0;
+  int path = FWD_EMPTY;
+  int form = -1;          // form of the path's family; -1: launch_sgemm_conv_variant chooses
+  bool implicit = false;  // one of the paths from FWD_DIRECT on: operands checked before err
+  bool bias_act = false;  // bias + activation fused into the path's epilogue
+  int epi_act = 0;        // the epilogue's activation (linear before a transcendental one)
+  bool act_tail = false;  // the transcendental activation in a pass of its own
+  bool needs_col = false;  // FWD_IM2COL: a col matrix, not the input planes
+  bool padded = false;     // FWD_IMPLICIT: gather from zero-padded copies of the images
+  int64_t chunk = 0;       // FWD_TILE / FWD_IMPLICIT: images per launch
+  // scratch in floats, 0 = slot not used: SLOT_COL (the col matrix when the
+  // caller passes no workspace; the slab), SLOT_STAGE1 (the padded images)
+  int64_t col_elems = 0, stage1_elems = 0;
+  int64_t conv_variant = -1;  // TNS_OPT_CONV_VARIANT as set (error messages)
+  int srss_quirk = 0;         // for the batch-norm passes of conv_forward_train
+};
+ConvFwdPlan plan_conv_forward(const ConvShape& s, int fused, bool bias_act, const Options& o);
+
+enum ConvDwPath { DW_RES = 0, DW_TILE, DW_SDOT, DW_GEMM };
+// dW: residue forms (dw_res.hip), implicit-im2col tile (dw_tile.hip), one
+// batched sdot launch + in-order add, the per-image NT GEMM loop
+struct ConvDwChoice {
+  int path = DW_GEMM;
+  int form = -1;
+  bool col = false;        // reads an im2col matrix
+  int64_t part_elems = 0;  // SLOT_DW: per-image (per-group) partial products
+};
+enum ConvDxPath {
+  DX_NONE = 0,  // no state.delta
+  DX_CONV1X1,   // conv1x1.hip on W^T, the add in its epilogue
+  DX_FUSED,     // conv_dx.hip: dX + col2im in one kernel
+  DX_CONV3,     // conv_tile4 dx3: implicit transposed 3x3 convolution
+  DX_CONV3S2,   // the same per pixel parity class of a stride-2 layer
+  DX_TILE,      // conv_tile4's k-major-A tile (+ col2im unless dx_direct)
+  DX_TN         // the TN GEMM (+ col2im unless dx_direct)
+};
+enum ConvBwdSched { BWD_SEQUENTIAL = 0, BWD_JOINED, BWD_PIPELINED };
+struct ConvBwdPlan {
+  int err = 0;
+  char msg[kPlanMsg] = {};
+  ConvShape s{};
+  ConvGeom g{};
+  bool empty = true;  // no delta element: nothing runs
+  bool has_bn = false, has_state_delta = false, delta_aligned16 = false;
+  int64_t i_m = 0, i_n = 0, i_k = 0, colSize = 0;  // dW is i_m x i_n over i_k pixels
+  bool bn_fused = false;     // try launch_bn_backward_fused first
+  bool derive_sums = false;  // Derivative + addSums in one pass
+  int srss_quirk = 0;
+  ConvDwChoice dw;
+  // the choice once a residue form picked by shape is withdrawn (its scratch
+  // refused); a forced one (dw_res_forced) keeps the error instead
+  ConvDwChoice dw_fallback;
+  bool dw_res_forced = false;
+  int dx = DX_NONE;
+  int dx_form = -1;
+  // the k-major-A form behind DX_CONV1X1 when that launch refuses the
+  // operands' alignment, and of DX_TILE; -1: the TN GEMM
+  int dx_tile = -1;
+  bool dx_tile_forced = false;  // its "does not fit" is an error, not a fall-through
+  bool dx_direct = false;       // the product adds into state.delta: no col2im
+  bool needs_col = false;       // the layer's col matrix is not its input
+  bool dx_col = false;          // dX writes a col matrix
+  int sched = BWD_SEQUENTIAL;   // wanted; what the context can do is run-time
+  // scratch in floats, 0 = slot not used: SLOT_BN, SLOT_RES_A / _B, SLOT_COL
+  // (and SLOT_COL_DX, a second one of the same size), SLOT_WT
+  int64_t bn_elems = 0, res_a_elems = 0, res_b_elems = 0, col_elems = 0, wt_elems = 0;
+};
+ConvBwdPlan plan_conv_backward(const ConvShape& s, bool has_bn, bool has_state_delta,
+                               bool delta_aligned16, const Options& o);
+
 }  // namespace tns
