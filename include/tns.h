@@ -334,6 +334,64 @@ int tns_hip_yolo_loss(tns_ctx* ctx, int64_t batch, int64_t anchors, int64_t clas
                       float truthThresh, float iouThresh, float iouNormalizer,
                       float objNormalizer, float* output, const float* truth, float* delta,
                       float* cost, float* stats, int64_t* counters);
+/* TNNet.Detections' per-layer part (nnet.pas:584-677): TYoloLayer.
+ * getDetectionCount + getDetections + correctBoxes (nyololayer.pas:378-498,
+ * getBox 105-122, not newCoords) for one layer and all images, bit for bit the
+ * CPU loop's rows.  output [batch][anchors][classes+5][h*w] is what
+ * tns_hip_yolo_forward left; mask (anchors entries) and biases (2*total
+ * floats) are HOST arrays, copied before the call returns; every other
+ * operand is on the device: counts int64[batch], boxes [batch][capacity][4]
+ * (x, y, w, h), objectness [batch][capacity], probs [batch][capacity][classes].
+ * A candidate (cell i, anchor a) is taken when its objectness is > thresh
+ * (strict; NaN is not taken: the reference's NaN check is commented out,
+ * lines 392-394, 424-426).  The taken candidates of image b become the rows
+ * counts[b], counts[b]+1, ... in the reference's order, cell i outer, anchor a
+ * inner: bbox = getBox(mask[a], .., col, row, netW, netH, h*w) after
+ * correctBoxes(imW, imH, netW, netH, relative, letter); objectness; prob[j] =
+ * objectness * class_j where that product is > thresh, else 0 (435-443).
+ * counts[b] then grows by the number of taken candidates, whether their rows
+ * fitted or not: rows at or beyond capacity are not written, and counts[b] >
+ * capacity afterwards is how the caller learns of it (the reference's count
+ * pass and fill pass in one).  So the layers of a network append into one
+ * buffer when called in network order on counts zeroed once.  Nothing outside
+ * the taken rows is written.  Not built: new_coords, the embedding output,
+ * TRegionLayer.  A letterbox whose scaled extent truncates to 0 divides by
+ * zero as the reference does; the result is then IEEE's, not an exception.
+ * TNS_ERR_ARG, before anything is launched or written: a negative size; netW,
+ * netH, imW or imH below 1 or above 2^24; a null operand where there is work
+ * (batch, anchors and h*w all above 0); a mask entry outside [0, total);
+ * anchors or total above 32; capacity outside [1, 4194304]; batch above 65535;
+ * a buffer beyond 2^31 elements.  batch == 0 is a successful no-op. */
+int tns_hip_yolo_detections(tns_ctx* ctx, int64_t batch, int64_t anchors, int64_t classes,
+                            int64_t h, int64_t w, int64_t total, const int64_t* mask,
+                            const float* biases, int64_t netW, int64_t netH, int64_t imW,
+                            int64_t imH, float thresh, int32_t relative, int32_t letter,
+                            const float* output, int64_t capacity, int64_t* counts, float* boxes,
+                            float* objectness, float* probs);
+/* TDetections.doNMSSort (ntypes.pas:1612-1649, Comparer 1554-1565, TBox.iou
+ * 1059-1108 in singles) on the rows tns_hip_yolo_detections left, in place on
+ * probs.  For image b the rows 0 .. min(counts[b], capacity)-1 whose
+ * objectness is not 0 take part (the reference swaps the zero-objectness rows
+ * out of `total`, 1619-1633).  For each class k on its own: the rows in order
+ * of prob[k] descending; a row whose prob[k] is still non-zero when the walk
+ * reaches it sets prob[k] of every later row to 0 whose bbox has an iou with
+ * it > thresh; a row already zeroed suppresses nothing.  Departures: (1) rows
+ * keep their place (the reference leaves the array permuted in the last
+ * class's sort order); per row the result is the same.  (2) Equal non-zero
+ * scores order the lower row first; the reference's QuickSort is not stable,
+ * so their order there is unspecified (ties at zero do not matter: a zero row
+ * suppresses nothing and zeroing it changes nothing).  NaN scores order by
+ * their bit pattern, above +Inf when positive.  Only prob entries that become
+ * 0 are written.  Any number of non-zero rows per class up to capacity:
+ * up to 2048 of one (image, class) are sorted on chip, more are walked by
+ * repeated selection with the same result.  doNMSObj and the DIoU / corners
+ * NMS kinds are not built.  TNS_ERR_ARG, before anything is launched or
+ * written: a negative size, capacity outside [1, 4194304], batch above 65535,
+ * a buffer beyond 2^31 elements, a null operand where there is work (batch
+ * and classes above 0).  batch == 0, or all counts 0, is a successful no-op. */
+int tns_hip_nms_sort(tns_ctx* ctx, int64_t batch, int64_t capacity, int64_t classes,
+                     const int64_t* counts, const float* boxes, const float* objectness,
+                     float* probs, float thresh);
 
 /* ---- max / local-average pooling (TMaxPoolLayer, nMaxPoolLayer.pas) ----- */
 /* Geometry, shared by the four entries: input [aBatch][c][h][w], output

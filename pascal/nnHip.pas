@@ -194,6 +194,18 @@ function tns_hip_yolo_loss(ctx: PTnsCtx; batch, anchors, classes, h, w, total: i
   mask: PInt64; biases: PSingle; maxBoxes, netW, netH: int64; ignoreThresh, truthThresh,
   iouThresh, iouNormalizer, objNormalizer: single; output, truth, delta, cost,
   stats: THipMem; counters: PInt64): longint; cdecl; external libtns;
+{ TYoloLayer.getDetectionCount + getDetections + correctBoxes (nyololayer.pas:378-498)
+  for one layer and all images: mask (SizeInt) and biases are host arrays; counts a
+  device int64[batch], each image's first row on entry, grown by its taken candidates;
+  boxes [batch][capacity][4], objectness [batch][capacity], probs [batch][capacity][classes] }
+function tns_hip_yolo_detections(ctx: PTnsCtx; batch, anchors, classes, h, w, total: int64;
+  mask: PInt64; biases: PSingle; netW, netH, imW, imH: int64; thresh: single; relative,
+  letter: longint; output: THipMem; capacity: int64; counts: PInt64; boxes, objectness,
+  probs: THipMem): longint; cdecl; external libtns;
+{ TDetections.doNMSSort (ntypes.pas:1612-1649) on those rows, in place on probs; rows
+  keep their place }
+function tns_hip_nms_sort(ctx: PTnsCtx; batch, capacity, classes: int64; counts: PInt64;
+  boxes, objectness, probs: THipMem; thresh: single): longint; cdecl; external libtns;
 
 { max / local-average pooling; indexes = TSizeIntTensor's device data }
 function tns_hip_maxpool_forward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; input: THipMem;
@@ -373,6 +385,8 @@ type
     procedure forwardAvgPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; output: TCUMem);
     procedure backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const delta: TCUMem; const h, w, stride_x, stride_y, padding, kernelSize: SizeInt);
     procedure yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);
+    procedure yoloDetections(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
+    procedure nmsSort(const batch, capacity, classes: SizeInt; const counts, boxes, objectness: TCUMem; probs: TCUMem; const thresh: single);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
     procedure upSample(const aBatch, aChannels, outHeight, outWidth: SizeInt; const &in: TCUMem; const stride: SizeInt; const isForward: longint; const scale: T; const &out: TCUMem; const zeroIn: integer = 0);
@@ -665,6 +679,25 @@ begin
     maxBoxes, netW, netH, ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer,
     THipMem(output), THipMem(truth), THipMem(delta), THipMem(cost), THipMem(stats),
     PInt64(counters)))
+end;
+
+procedure TNNHip<T>.yoloDetections(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
+begin
+  { one [yolo] layer's getDetections + correctBoxes for every image; call it for
+    the layers in network order on counts zeroed once (fill over 2*batch
+    singles) and the rows stand as TNNet.Detections leaves them.  counts[b] >
+    capacity afterwards: image b's rows did not all fit }
+  check(tns_hip_yolo_detections(FCtx, batch, anchors, classes, h, w, total, PInt64(mask), biases,
+    netW, netH, imW, imH, thresh, ord(relative), ord(letter), THipMem(output), capacity,
+    PInt64(counts), THipMem(boxes), THipMem(objectness), THipMem(probs)))
+end;
+
+procedure TNNHip<T>.nmsSort(const batch, capacity, classes: SizeInt; const counts, boxes, objectness: TCUMem; probs: TCUMem; const thresh: single);
+begin
+  { TDetections.doNMSSort per image and class, in place on probs; rows keep
+    their place }
+  check(tns_hip_nms_sort(FCtx, batch, capacity, classes, PInt64(counts), THipMem(boxes),
+    THipMem(objectness), THipMem(probs), thresh))
 end;
 
 procedure TNNHip<T>.im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);

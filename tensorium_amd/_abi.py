@@ -199,6 +199,12 @@ PROTOTYPES.update({
     "tns_hip_yolo_loss": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, C.POINTER(i64),
                                     C.POINTER(f32), i64, i64, i64, f32, f32, f32, f32, f32, fptr,
                                     fptr, fptr, fptr, fptr, vp]),
+    # detections: mask (int64) and biases host arrays; counts a device
+    # int64[batch]; output, boxes, objectness, probs device floats
+    "tns_hip_yolo_detections": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, C.POINTER(i64),
+                                          C.POINTER(f32), i64, i64, i64, i64, f32, i32, i32, fptr,
+                                          i64, vp, fptr, fptr, fptr]),
+    "tns_hip_nms_sort": (C.c_int, [vp, i64, i64, i64, vp, fptr, fptr, fptr, f32]),
     # pooling: the indexes operand is an int64 device buffer
     "tns_hip_maxpool_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, i64, i64, i64, i64, i64,
                                           i64, i64, vp, fptr]),

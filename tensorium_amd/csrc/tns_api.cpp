@@ -1004,6 +1004,85 @@ int tns_hip_yolo_loss(tns_ctx* c, int64_t batch, int64_t anchors, int64_t classe
                     "yolo loss");
 }
 
+int tns_hip_yolo_detections(tns_ctx* c, int64_t batch, int64_t anchors, int64_t classes, int64_t h,
+                            int64_t w, int64_t total, const int64_t* mask, const float* biases,
+                            int64_t netW, int64_t netH, int64_t imW, int64_t imH, float thresh,
+                            int32_t relative, int32_t letter, const float* output,
+                            int64_t capacity, int64_t* counts, float* boxes, float* objectness,
+                            float* probs) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (batch < 0 || anchors < 0 || classes < 0 || h < 0 || w < 0 || total < 0 || netW < 1 ||
+      netH < 1 || imW < 1 || imH < 1)
+    return set_error(TNS_ERR_ARG,
+                     "yolo detections: negative size, or a network / image extent below 1");
+  if (capacity < 1 || capacity > kDetMaxCapacity)
+    return set_error(TNS_ERR_ARG, "yolo detections: capacity %lld outside [1, %d]",
+                     (long long)capacity, kDetMaxCapacity);
+  if (anchors > kYoloMaxAnchors || total > kYoloMaxAnchors)
+    return set_error(TNS_ERR_ARG, "yolo detections: more than %d anchors", kYoloMaxAnchors);
+  const int64_t lim = 0x3fffffff;
+  if (batch > 65535 || classes > lim || h > lim || w > lim || netW > (1 << 24) ||
+      netH > (1 << 24) || imW > (1 << 24) || imH > (1 << 24) || h * w > lim ||
+      h * w * anchors > lim || batch * anchors > lim ||
+      batch * anchors * (classes + 5) > 0x7fff0000 / std::max<int64_t>(h * w, 1) ||
+      batch * capacity > 0x7fff0000 / std::max<int64_t>(classes, 4))
+    return set_error(TNS_ERR_ARG,
+                     "yolo detections: batch beyond 65535, an extent beyond 2^24, or a buffer "
+                     "beyond 2^31 elements");
+  const bool work = batch > 0 && anchors > 0 && h * w > 0;
+  if (work && (!output || !counts || !boxes || !objectness || (classes > 0 && !probs) || !mask ||
+               (total > 0 && !biases)))
+    return set_error(TNS_ERR_ARG, "yolo detections: null operand");
+  DetParams p{};
+  for (int64_t i = 0; work && i < anchors; ++i) {
+    if (mask[i] < 0 || mask[i] >= total)
+      return set_error(TNS_ERR_ARG, "yolo detections: mask[%lld] = %lld outside [0, %lld)",
+                       (long long)i, (long long)mask[i], (long long)total);
+    p.mask[i] = (int)mask[i];
+  }
+  if (!work) return TNS_OK;
+  for (int64_t i = 0; i < 2 * total; ++i) p.biases[i] = biases[i];
+  p.batch = (int)batch, p.n = (int)anchors, p.classes = (int)classes, p.h = (int)h, p.w = (int)w;
+  p.netW = (int)netW, p.netH = (int)netH, p.imW = (int)imW, p.imH = (int)imH;
+  p.relative = relative != 0, p.letter = letter != 0, p.capacity = (int)capacity;
+  p.thresh = thresh;
+  if (int r = check_ops(c,
+                        {span(boxes, batch * capacity * 4), span(objectness, batch * capacity),
+                         span(probs, batch * capacity * classes),
+                         span(reinterpret_cast<float*>(counts), 2 * batch)},
+                        {span(output, batch * anchors * (classes + 5) * h * w)}))
+    return r;
+  float* scratch = nullptr;
+  if (int r = ensure_scratch(c, SLOT_YOLO, detections_scratch_floats(p), &scratch)) return r;
+  return hip_status(launch_yolo_detections(p, output, counts, boxes, objectness, probs, scratch,
+                                           c->stream),
+                    "yolo detections");
+}
+
+int tns_hip_nms_sort(tns_ctx* c, int64_t batch, int64_t capacity, int64_t classes,
+                     const int64_t* counts, const float* boxes, const float* objectness,
+                     float* probs, float thresh) {
+  if (!c) return set_error(TNS_ERR_ARG, "null tns_ctx");
+  if (batch < 0 || classes < 0) return set_error(TNS_ERR_ARG, "nms sort: negative size");
+  if (capacity < 1 || capacity > kDetMaxCapacity)
+    return set_error(TNS_ERR_ARG, "nms sort: capacity %lld outside [1, %d]", (long long)capacity,
+                     kDetMaxCapacity);
+  if (batch > 65535 || classes > 0x3fffffff ||
+      batch * capacity > 0x7fff0000 / std::max<int64_t>(classes, 4))
+    return set_error(TNS_ERR_ARG,
+                     "nms sort: batch beyond 65535, or a buffer beyond 2^31 elements");
+  if (batch == 0 || classes == 0) return TNS_OK;
+  if (!counts || !boxes || !objectness || !probs)
+    return set_error(TNS_ERR_ARG, "nms sort: null operand");
+  if (int r = check_ops(c, {span(probs, batch * capacity * classes)},
+                        {span(boxes, batch * capacity * 4), span(objectness, batch * capacity),
+                         span(reinterpret_cast<const float*>(counts), 2 * batch)}))
+    return r;
+  return hip_status(launch_nms_sort((int)batch, (int)capacity, (int)classes, counts, boxes,
+                                    objectness, probs, thresh, c->stream),
+                    "nms sort");
+}
+
 // TNNCuda.forwardMaxPool / backwardMaxPool (nncuda.pas:132-133) and the local
 // average pool over the same geometry
 namespace {

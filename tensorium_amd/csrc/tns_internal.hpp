@@ -368,6 +368,23 @@ int64_t yolo_loss_scratch_floats(int64_t n);
 hipError_t launch_yolo_loss(const YoloLossParams& p, float* out, const float* truth, float* delta,
                             float* cost, float* stats, unsigned long long* counters,
                             float* scratch, hipStream_t s);
+// detections.hip: getDetections + correctBoxes of one [yolo] layer into the
+// rows behind counts[b] (collect), and doNMSSort on such rows (nms).  mask and
+// biases by value as above.  scratch: detections_scratch_floats(p) floats.
+constexpr int kDetMaxCapacity = 1 << 22;  // rows an image; a row index fits a key's low word
+struct DetParams {
+  int batch, n, classes, h, w, netW, netH, imW, imH, relative, letter, capacity;
+  float thresh;
+  int mask[kYoloMaxAnchors];
+  float biases[2 * kYoloMaxAnchors];
+};
+int64_t detections_scratch_floats(const DetParams& p);
+hipError_t launch_yolo_detections(const DetParams& p, const float* out, int64_t* counts,
+                                  float* boxes, float* objectness, float* probs, float* scratch,
+                                  hipStream_t s);
+hipError_t launch_nms_sort(int batch, int capacity, int classes, const int64_t* counts,
+                           const float* boxes, const float* objectness, float* probs,
+                           float thresh, hipStream_t s);
 hipError_t launch_bias_activate(float* dst, int64_t nFilters, int64_t blockSize,
                                 const float* bias, int64_t batch, int act, hipStream_t s);
 hipError_t launch_derive(const float* x, int64_t n, int act, float* delta, hipStream_t s);

@@ -1,7 +1,7 @@
 // yolo_loss.hip — the training part of TYoloLayer.forward (nyololayer.pas:
 // 835-1003 with processBatch 500-774, deltaBox 124-202, deltaClass 204-251,
 // averageDeltas 253-269, compareClass 272-281, getBox 105-122 and box_iou,
-// ntypes.pas:1059-1108) for one [yolo] layer, on the device: truth boxes in,
+// ntypes.pas:1059-1108, in yolo_box.hpp) for one [yolo] layer, on the device: truth boxes in,
 // the layer's delta and cost[0] out.  Scope: iou_loss=mse, iou_thresh_kind=
 // iou, scale_x_y=1, none of focal_loss / objectness_smooth / label_smooth_eps
 // / new_coords / counters_per_class / map / embedding_layer, [net] without
@@ -31,35 +31,10 @@
 // to a single; every other expression is single with each operation rounded.
 // The type of each sub-expression stands next to it: [s] single, [d] double.
 #include "tns_internal.hpp"
+#include "yolo_box.hpp"
 
 namespace tns {
 namespace {
-
-struct Box {
-  float x, y, w, h;
-};
-
-// overlap (ntypes.pas:1059-1075), singles throughout
-__device__ __forceinline__ float overlap(float x1, float w1, float x2, float w2) {
-  const float l1 = x1 - w1 / 2.0f;  // [s] w1/2 [s], then the difference [s]
-  const float l2 = x2 - w2 / 2.0f;  // [s]
-  const float left = l1 > l2 ? l1 : l2;
-  const float r1 = x1 + w1 / 2.0f;  // [s]
-  const float r2 = x2 + w2 / 2.0f;  // [s]
-  const float right = r1 < r2 ? r1 : r2;
-  return right - left;  // [s]
-}
-
-// box_iou (ntypes.pas:1077-1108): I = box_intersection, U = a.w*a.h + b.w*b.h
-// - I; 0 when either is 0
-__device__ __forceinline__ float box_iou(const Box& a, const Box& b) {
-  const float w = overlap(a.x, a.w, b.x, b.w);
-  const float h = overlap(a.y, a.h, b.y, b.h);
-  const float I = (w < 0.0f || h < 0.0f) ? 0.0f : w * h;  // [s]
-  const float U = a.w * a.h + b.w * b.h - I;  // [s] two products, their sum, minus I
-  if (I == 0.0f || U == 0.0f) return 0.0f;
-  return I / U;  // [s]
-}
 
 // getBox (nyololayer.pas:105-122), not newCoords, from the cell's four box
 // entries o[0..3]

@@ -45,7 +45,7 @@ from pathlib import Path
 
 import numpy as np
 
-from ._abi import ACT
+from ._abi import ACT, TnsError
 
 SEPS = np.float32(0.000001)  # sEPSILON, ntensors.pas:95
 
@@ -1152,6 +1152,36 @@ class _RnnLayers:
                                self.net.batch, decay, momentum, st.get("scales"), st.get("su"))
 
 
+def detection_rows_to_host(torch, taken, cap, classes, boxes, obj, probs, pin=None):
+    """The first taken[b] rows of every image b out of the device row buffers
+    (``cap`` rows an image) as NumPy arrays: asynchronous copies of exactly
+    those rows into one pinned host buffer, then one synchronisation.
+    ``pin``: the buffer of an earlier call, reused while it is large enough.
+    Returns ([(boxes [n, 4], objectness [n], probs [n, classes])], pin)."""
+    total = sum(taken)
+    need = max(total * (5 + classes), 1)
+    if pin is None or pin.numel() < need:
+        pin = torch.empty(need, dtype=torch.float32).pin_memory()
+    hb, ho, hp = pin[:4 * total], pin[4 * total:5 * total], pin[5 * total:need]
+    at = 0
+    for b, n in enumerate(taken):
+        if n:
+            hb[4 * at:4 * (at + n)].copy_(boxes[b * cap * 4:(b * cap + n) * 4], non_blocking=True)
+            ho[at:at + n].copy_(obj[b * cap:b * cap + n], non_blocking=True)
+            if classes:
+                hp[classes * at:classes * (at + n)].copy_(
+                    probs[b * cap * classes:(b * cap + n) * classes], non_blocking=True)
+        at += n
+    torch.cuda.current_stream().synchronize()
+    res, at = [], 0
+    for n in taken:
+        res.append((hb[4 * at:4 * (at + n)].numpy().reshape(n, 4).copy(),
+                    ho[at:at + n].numpy().copy(),
+                    hp[classes * at:classes * (at + n)].numpy().reshape(n, classes).copy()))
+        at += n
+    return res, pin
+
+
 class HipDarknet(_RnnLayers, _LstmLayers):
     """TNNet.forward over a darknet layer plan on the HIP backend (nnet.pas:
     275-310 selects forwardGPU per layer): every layer's output stays in a
@@ -1200,7 +1230,8 @@ class HipDarknet(_RnnLayers, _LstmLayers):
 
     def forward(self, x):
         """x: device tensor [batch, c, h, w] (contiguous).  Returns the per-
-        layer output buffers (the yolo layers' are the detections)."""
+        layer output buffers (``detections`` turns the yolo layers' into
+        boxes and scores)."""
         hip, B = self.hip, self.net.batch
         prev = x
         for l in self.net.layers:
@@ -1252,6 +1283,62 @@ class HipDarknet(_RnnLayers, _LstmLayers):
                 hip.ActivateArray(B * l.in_size, out, 0, l.activation)
             prev = out
         return self.out
+
+    def detections(self, im_w, im_h, thresh=0.5, relative=False, letter=False, nms=None,
+                   capacity=None):
+        """TNNet.Detections (nnet.pas:584-677) for every image of the batch,
+        then TDetections.doNMSSort (ntypes.pas:1612-1649) when ``nms`` is a
+        threshold, on the device; call it after ``forward``.  The [yolo]
+        layers are collected in network order into one row buffer
+        (TNNHip.yoloDetections appends through a per-image device counter),
+        so the rows stand in the reference's order: layer, then cell, then
+        anchor.  Returns, per image, ``(boxes [rows, 4], objectness [rows],
+        probs [rows, classes])`` as NumPy arrays of exactly the taken rows;
+        only the counters and those rows are copied back.  After NMS the rows
+        keep their place (the reference leaves them in the last class's sort
+        order).  ``capacity``: rows an image; the default, the sum of
+        anchors*h*w over the yolo layers, cannot overflow, a smaller one
+        raises TnsError when an image has more taken candidates."""
+        hip, torch, B = self.hip, self.torch, self.net.batch
+        yolos = [l for l in self.net.layers if l.kind == "yolo"]
+        if not yolos:
+            raise ValueError("detections: the network has no [yolo] layer")
+        # the reference sizes every row's prob by the first layer's classes
+        # (nnet.pas:625) and lets a later layer write its own count into it
+        if len({l.classes for l in yolos}) > 1:
+            raise ValueError("detections: the [yolo] layers disagree on classes: "
+                             f"{[l.classes for l in yolos]}")
+        bad = [f"layer {l.index} {k}" for l in yolos for k in l.unbuilt
+               if k in ("new_coords", "embedding_layer")]
+        if bad:
+            raise ValueError("detections: not built: " + ", ".join(bad))
+        classes = yolos[0].classes
+        cap = sum(l.anchors * l.h * l.w for l in yolos) if capacity is None else int(capacity)
+        if cap < 1:
+            raise ValueError(f"detections: capacity {cap}")
+        key = (cap, classes)
+        if getattr(self, "_det_key", None) != key:
+            self._det_key = key
+            self._det = (torch.zeros(B, dtype=torch.int64, device="cuda"),
+                         torch.empty(B * cap * 4, device="cuda"),
+                         torch.empty(B * cap, device="cuda"),
+                         torch.empty(B * cap * max(classes, 1), device="cuda"))
+        counts, boxes, obj, probs = self._det
+        hip.fill(2 * B, counts.data_ptr(), 0, 0.0, 1)  # int64 zeros, on the backend's stream
+        for l in yolos:
+            hip.yoloDetections(B, l.anchors, classes, l.h, l.w, l.total, l.mask, l.biases,
+                               self.net.w, self.net.h, im_w, im_h, thresh, relative, letter,
+                               self.out[l.index], cap, counts, boxes, obj, probs)
+        if nms is not None:
+            hip.nmsSort(B, cap, classes, counts, boxes, obj, probs, nms)
+        hip.finish()
+        taken = counts.cpu().tolist()
+        for b, n in enumerate(taken):
+            if n > cap:
+                raise TnsError(f"detections: image {b} has {n} taken candidates, capacity {cap}")
+        res, self._det_pin = detection_rows_to_host(torch, taken, cap, classes, boxes, obj, probs,
+                                                    getattr(self, "_det_pin", None))
+        return res
 
 
 class HipDarknetTrain(_RnnLayers, _LstmLayers):

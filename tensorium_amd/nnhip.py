@@ -325,6 +325,34 @@ class TNNHip:
             float(objNormalizer), _ptr(output), _ptr(truth), _ptr(delta), _ptr(cost), _ptr(stats),
             _iptr(counters)))
 
+    def yoloDetections(self, batch, anchors, classes, h, w, total, mask, biases, netW, netH, imW,
+                       imH, thresh, relative, letter, output, capacity, counts, boxes,
+                       objectness, probs):
+        """TYoloLayer.getDetections + correctBoxes for one layer and all images
+        (tns_hip_yolo_detections).  mask / biases: host sequences (len anchors
+        / 2*total); output, boxes [batch][capacity][4], objectness
+        [batch][capacity], probs [batch][capacity][classes]: device float
+        tensors; counts: a device int64[batch], read as each image's first row
+        and grown by the image's taken candidates."""
+        mask = [int(m) for m in mask]
+        biases = [float(v) for v in biases]
+        if len(mask) != anchors or len(biases) != 2 * total:
+            raise TnsError(f"yoloDetections: {len(mask)} mask entries for {anchors} anchors, "
+                           f"{len(biases)} biases for total={total}")
+        m = (C.c_int64 * max(len(mask), 1))(*mask)
+        bs = (C.c_float * max(len(biases), 1))(*biases)
+        check(self.lib.tns_hip_yolo_detections(
+            self.ctx, batch, anchors, classes, h, w, total, m, bs, netW, netH, imW, imH,
+            float(thresh), int(bool(relative)), int(bool(letter)), _ptr(output), capacity,
+            _iptr(counts), _ptr(boxes), _ptr(objectness), _ptr(probs)))
+
+    def nmsSort(self, batch, capacity, classes, counts, boxes, objectness, probs, thresh):
+        """TDetections.doNMSSort on the rows yoloDetections left, in place on
+        probs (tns_hip_nms_sort); rows keep their place."""
+        check(self.lib.tns_hip_nms_sort(self.ctx, batch, capacity, classes, _iptr(counts),
+                                        _ptr(boxes), _ptr(objectness), _ptr(probs),
+                                        float(thresh)))
+
     # -- layer drivers ------------------------------------------------------------
     def conv2d(self, batch, C_, H, W, input, weights, filters, kH, kW, wPadding, hPadding,
                xStride, yStride, xDilation, yDilation, workspace, out):
