@@ -262,7 +262,10 @@ int tns_hip_clamp(tns_ctx* ctx, int64_t N, float alpha, const float* src, float*
 /* TNNCuda.addvv / subvv / mulvv / fmavv (nncuda.pas:120-123):
  * dst[i*incc] = src1[i*inca] op src2[i*incb] (offsets in elements); fmavv:
  * src1*src2 rounded, then + src3 rounded (no fused multiply-add, as the CPU
- * sfmavss).  fmavss (nncuda.pas:137): dst = src*scalar + bias over N
+ * sfmavss).  The increments are taken as they come, as the reference's
+ * kernels take them: a negative one walks downward from the pointer + offset
+ * (which then names the operand's highest element), 0 reads one element N
+ * times.  fmavss (nncuda.pas:137): dst = src*scalar + bias over N
  * contiguous elements at offset.  inverseSqrt (nncuda.pas:151):
  * dst = 1/sqrt(max(src, 1e-6)) strided; alpha unused (as the reference). */
 int tns_hip_addvv(tns_ctx* ctx, int64_t N, const float* src1, int64_t src1Offset, int64_t inca,

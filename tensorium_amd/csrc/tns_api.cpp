@@ -59,8 +59,10 @@ namespace {
 // dimension ld, batch copies every stride
 Span span_mat(const float* p, int64_t rows, int64_t cols, int64_t ld, int64_t stride,
               int64_t batch) {
-  if (rows <= 0 || cols <= 0 || batch <= 0) return Span{};
-  return span(p, (batch - 1) * (stride > 0 ? stride : 0) + (rows - 1) * ld + cols);
+  if (rows <= 0 || cols <= 0 || batch <= 0 || !p) return Span{};
+  // (a negative stride puts the later copies below p)
+  const int64_t back = stride < 0 ? (batch - 1) * stride : 0;
+  return span(p + back, (stride > 0 ? (batch - 1) * stride : -back) + (rows - 1) * ld + cols);
 }
 
 // ---- default context for the host-pointer API (boundary A) ---------------

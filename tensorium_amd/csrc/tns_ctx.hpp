@@ -224,17 +224,22 @@ inline int check_ctx(tns_ctx* c, bool join = true) {
   return join ? join_side(c) : TNS_OK;
 }
 
-// an operand's extent: n elements every |inc| from p (empty when p is null
-// or n <= 0)
+// an operand's extent: n elements every inc from p (empty when p is null or
+// n <= 0).  A negative inc walks downward: p is the highest element touched.
+// inc == 0 touches p alone and claims n elements (conservative)
 struct Span {
   uintptr_t lo = 0, hi = 0;
 };
 inline Span span(const float* p, int64_t n, int64_t inc = 1) {
   Span s;
   if (!p || n <= 0) return s;
-  const int64_t a = inc < 0 ? -inc : (inc == 0 ? 1 : inc);
+  if (inc < 0) {
+    s.lo = (uintptr_t)(p + (n - 1) * inc);
+    s.hi = (uintptr_t)(p + 1);
+    return s;
+  }
   s.lo = (uintptr_t)p;
-  s.hi = (uintptr_t)(p + (n - 1) * a + 1);
+  s.hi = (uintptr_t)(p + (n - 1) * (inc == 0 ? 1 : inc) + 1);
   return s;
 }
 // every non-conv entry point: the context exists, and — during a pipelined

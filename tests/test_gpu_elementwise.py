@@ -132,6 +132,62 @@ def test_tnncuda_vector_ops(hip, torch_cuda):
     assert np.array_equal(out.cpu().numpy()[1::2], ref)
 
 
+VV_INCS = (-2, -1, 0, 1, 3)
+
+
+@pytest.mark.parametrize("n", [1, 7, 257])
+@pytest.mark.parametrize("name", ["addvv", "subvv", "mulvv", "fmavv"])
+def test_vector_ops_negative_and_zero_increments(hip, torch_cuda, name, n):
+    """addvv / subvv / mulvv / fmavv with an increment of -2, -1, 0, 1 or 3 on
+    each operand in turn (the others at 1), bit for bit NumPy's: element i of
+    an operand is at i*inc from the pointer + offset, as the reference's
+    kernels index it (nncuda.pas:897-950 pass the increments through as they
+    come).  A negative increment walks downward, so the offset names the
+    operand's last stored element and every index stays inside the buffer; 0
+    reads one element n times.  dst with increment 0 is one element written n
+    times: the sources then have increment 0 too, so that every write is the
+    same value whatever the order.  Nothing outside the n elements is
+    written."""
+    T = torch_cuda
+    rng = np.random.default_rng(n)
+    nsrc = 3 if name == "fmavv" else 2
+    G = 8                                    # sentinels on either side
+    f32 = np.float32
+
+    def operand(inc, fill):
+        span = (n - 1) * abs(inc) + 1
+        h = np.full(span + 2 * G, SENT, f32)
+        if fill:
+            h[G:G + span] = rng.uniform(-2, 2, span).astype(f32)
+        off = G + (span - 1 if inc < 0 else 0)
+        return h, off, off + np.arange(n) * inc       # buffer, offset, element indices
+
+    for which in range(nsrc + 1):
+        for inc in VV_INCS:
+            incs = [1] * (nsrc + 1)
+            incs[which] = inc
+            if which == nsrc and inc == 0:
+                incs = [0] * (nsrc + 1)
+            srcs = [operand(i, True) for i in incs[:nsrc]]
+            dh, doff, didx = operand(incs[nsrc], False)
+            assert all(0 <= ix.min() and ix.max() < h.size for h, _, ix in srcs + [(dh, doff, didx)])
+            v = [h[ix] for h, _, ix in srcs]
+            r = {"addvv": lambda: v[0] + v[1], "subvv": lambda: v[0] - v[1],
+                 "mulvv": lambda: v[0] * v[1],
+                 "fmavv": lambda: (v[0] * v[1]).astype(f32) + v[2]}[name]().astype(f32)
+            want = dh.copy()
+            for i in range(n):
+                want[didx[i]] = r[i]
+            dev_srcs = [T.from_numpy(h).cuda() for h, _, _ in srcs]
+            out = T.from_numpy(dh).cuda()
+            args = [n]
+            for d, (_, off, _), i in zip(dev_srcs, srcs, incs):
+                args += [d, off, i]
+            getattr(hip, name)(*args, out, doff, incs[nsrc])
+            hip.finish()
+            assert same(out.cpu().numpy(), want), (name, n, which, inc)
+
+
 # ---- dispatch branches, grid-stride trips, alignment and increments ----------
 ALL_ACTS = EXACT + TRANSC
 G = 16384 * 256          # grid cap (grid_for / blocks_for) x block size
