@@ -396,6 +396,57 @@ int tns_hip_nms_sort(tns_ctx* ctx, int64_t batch, int64_t capacity, int64_t clas
                      const int64_t* counts, const float* boxes, const float* objectness,
                      float* probs, float thresh);
 
+/* ---- image preprocessing (TImageData, ntypes.pas:837-947; image.hip) ----
+ * TImageData.resize, or with letter != 0 letterBox / letterBoxEx (resize,
+ * fill 0.5, Embed), of `count` images of differing sizes into the network
+ * input dst [count][channels][netH][netW] on the device, in one launch a
+ * batch, bit for bit the reference's values; every element of dst is written.
+ * Sources: interleaved bytes as decoders deliver them (h rows of w pixels,
+ * pixelStride bytes a pixel with channel k at byte k, rowStride bytes a row),
+ * or planar floats, TImageData's own layout ([channels][h] rows of w floats,
+ * rowStride floats a row, so a plane is h*rowStride floats).  src is a device
+ * pointer; geom is a HOST array int64[count][4] = {offset, w, h, rowStride}
+ * per image, offset the image's first element from src (bytes, or floats),
+ * copied before the call returns.  placed, optional, is a HOST array
+ * int64[count][4] that receives {new_w, new_h, dx, dy} per image: the resize
+ * target and where it sits in the net input.  Without letter that is {netW,
+ * netH, 0, 0}.  With letter: if netW*h < netH*w (the exact form of (aWidth /
+ * self.w) < (aHeight / self.h)) new_w = netW, new_h = (h*netW) div w, else
+ * new_h = netH, new_w = (w*netH) div h; dx = (netW-new_w) div 2, dy likewise;
+ * every pixel outside the rectangle is 0.5.  (letterBoxEx's ratio is
+ * single(netW/w) in the first branch, single(netH/h) in the other: the caller
+ * has both operands.)
+ * The resize, for target pixel (x, r), channel k, in singles with every
+ * product and sum rounded and no FMA: w_scale = single((w-1)/(new_w-1)),
+ * h_scale likewise; P(y) = src(w-1, y) if x = new_w-1 or w = 1, else
+ * (1-dx)*src(ix, y) + dx*src(ix+1, y) with sx = x*w_scale, ix = trunc(sx),
+ * dx = sx-ix; then sy = r*h_scale, iy = trunc(sy), dy = sy-iy, val =
+ * (1-dy)*P(iy), and unless r = new_h-1 or h = 1, val += dy*P(iy+1).  The last
+ * row is not special-cased as the last column is: where single(new_h-1)*
+ * h_scale rounds below h-1 (16 -> 416 rows, 479 -> 416, ...) it is
+ * (1-dy)*P(h-2) with dy just below 1, a near-black row, as in the reference.
+ * A byte b becomes a float through a 256-entry table, tableKind 0:
+ * single((b*257)/65280), the FPC loader's TFPColor word over $ff00
+ * (ntypes.pas:749-752; 255 maps above 1); 1: single(b/255), the Delphi
+ * loader's (716-718); 2: table, a HOST array of 256 floats, copied before the
+ * call returns.
+ * Both entries join a pending dW of the pipelined conv backward on every
+ * call (they write the network input, which that dW reads).
+ * TNS_ERR_ARG, before anything is launched or written: a null operand where
+ * count > 0 (src, geom, dst; table under tableKind 2); count outside [0,
+ * 2^20]; channels outside 1..4 for bytes (1..1024 for floats); pixelStride <
+ * channels or above 32768; tableKind outside 0..2; a negative offset; a rowStride shorter
+ * than a row; w, h, netW or netH outside [1, 32768]; a resize target (netW x
+ * netH, or new_w x new_h) below 2 either way, where the reference divides by
+ * zero.  count == 0 is a successful no-op. */
+int tns_image_bytes_to_input(tns_ctx* ctx, int64_t count, const uint8_t* src, const int64_t* geom,
+                             int64_t channels, int64_t pixelStride, int32_t tableKind,
+                             const float* table, int64_t netW, int64_t netH, int32_t letter,
+                             float* dst, int64_t* placed);
+int tns_image_floats_to_input(tns_ctx* ctx, int64_t count, const float* src, const int64_t* geom,
+                              int64_t channels, int64_t netW, int64_t netH, int32_t letter,
+                              float* dst, int64_t* placed);
+
 /* ---- max / local-average pooling (TMaxPoolLayer, nMaxPoolLayer.pas) ----- */
 /* Geometry, shared by the four entries: input [aBatch][c][h][w], output
  * [aBatch][outC][outH][outW] with outC == c, outH == (h + padding -

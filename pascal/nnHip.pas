@@ -207,6 +207,18 @@ function tns_hip_yolo_detections(ctx: PTnsCtx; batch, anchors, classes, h, w, to
 function tns_hip_nms_sort(ctx: PTnsCtx; batch, capacity, classes: int64; counts: PInt64;
   boxes, objectness, probs: THipMem; thresh: single): longint; cdecl; external libtns;
 
+{ TImageData.resize / letterBox / letterBoxEx (ntypes.pas:837-947) of count images into the
+  net input dst [count][channels][netH][netW]: src on the device (interleaved bytes, or
+  planar singles); geom a host int64[count][4] = offset, w, h, rowStride per image; placed
+  (may be nil) a host int64[count][4] that receives new_w, new_h, dx, dy; tableKind 0 the
+  FPC loader's b*257/$ff00, 1 the Delphi loader's b/$ff, 2 table (256 host singles) }
+function tns_image_bytes_to_input(ctx: PTnsCtx; count: int64; src: pointer; geom: PInt64;
+  channels, pixelStride: int64; tableKind: longint; table: PSingle; netW, netH: int64;
+  letter: longint; dst: THipMem; placed: PInt64): longint; cdecl; external libtns;
+function tns_image_floats_to_input(ctx: PTnsCtx; count: int64; src: THipMem; geom: PInt64;
+  channels, netW, netH: int64; letter: longint; dst: THipMem;
+  placed: PInt64): longint; cdecl; external libtns;
+
 { max / local-average pooling; indexes = TSizeIntTensor's device data }
 function tns_hip_maxpool_forward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64; input: THipMem;
   c, h, w, stride_x, stride_y, padding, kernelSize: int64; indexes: PInt64;
@@ -387,6 +399,7 @@ type
     procedure yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);
     procedure yoloDetections(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
     procedure nmsSort(const batch, capacity, classes: SizeInt; const counts, boxes, objectness: TCUMem; probs: TCUMem; const thresh: single);
+    procedure imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64 = nil);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
     procedure upSample(const aBatch, aChannels, outHeight, outWidth: SizeInt; const &in: TCUMem; const stride: SizeInt; const isForward: longint; const scale: T; const &out: TCUMem; const zeroIn: integer = 0);
@@ -698,6 +711,21 @@ begin
     their place }
   check(tns_hip_nms_sort(FCtx, batch, capacity, classes, PInt64(counts), THipMem(boxes),
     THipMem(objectness), THipMem(probs), thresh))
+end;
+
+procedure TNNHip<T>.imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64);
+begin
+  { TImageData.resize (letter: letterBoxEx) of count images straight into the
+    net input, one launch: what img.resize(netW, netH) / img.letterBoxEx leave in
+    data, without the host pass and with the decoded bytes crossing instead of
+    singles.  geom and placed are host arrays of 4 int64 an image (tns.h).
+    Joins a pending dW on every call }
+  if isBytes then
+    check(tns_image_bytes_to_input(FCtx, count, pointer(src), geom, channels, pixelStride,
+      tableKind, table, netW, netH, ord(letter), THipMem(dst), placed))
+  else
+    check(tns_image_floats_to_input(FCtx, count, THipMem(src), geom, channels, netW, netH,
+      ord(letter), THipMem(dst), placed))
 end;
 
 procedure TNNHip<T>.im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);

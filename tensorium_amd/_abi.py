@@ -205,6 +205,12 @@ PROTOTYPES.update({
                                           C.POINTER(f32), i64, i64, i64, i64, f32, i32, i32, fptr,
                                           i64, vp, fptr, fptr, fptr]),
     "tns_hip_nms_sort": (C.c_int, [vp, i64, i64, i64, vp, fptr, fptr, fptr, f32]),
+    # image preprocessing: src and dst on the device; geom, table and placed
+    # host arrays
+    "tns_image_bytes_to_input": (C.c_int, [vp, i64, vp, C.POINTER(i64), i64, i64, i32,
+                                           C.POINTER(f32), i64, i64, i32, fptr, C.POINTER(i64)]),
+    "tns_image_floats_to_input": (C.c_int, [vp, i64, fptr, C.POINTER(i64), i64, i64, i64, i32,
+                                            fptr, C.POINTER(i64)]),
     # pooling: the indexes operand is an int64 device buffer
     "tns_hip_maxpool_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, i64, i64, i64, i64, i64,
                                           i64, i64, vp, fptr]),

@@ -1085,6 +1085,86 @@ int tns_hip_nms_sort(tns_ctx* c, int64_t batch, int64_t capacity, int64_t classe
                     "nms sort");
 }
 
+// TImageData.resize / letterBox / letterBoxEx (ntypes.pas:837-947) into the
+// network input.  Not a TNNCuda method, hence tns_image_*; instead of a place
+// in the hazard table the two entries join the side stream on every call
+namespace {
+int image_to_input(tns_ctx* c, bool bytes, int64_t count, const void* src, const int64_t* geom,
+                   int64_t channels, int64_t pixelStride, int32_t tableKind, const float* table,
+                   int64_t netW, int64_t netH, int32_t letter, float* dst, int64_t* placed) {
+  if (int r = check_ctx(c)) return r;
+  const int64_t lim = kImageMaxExtent;
+  if (count < 0 || count > (1 << 20))
+    return set_error(TNS_ERR_ARG, "image: count %lld outside [0, 2^20]", (long long)count);
+  if (netW < 1 || netW > lim || netH < 1 || netH > lim)
+    return set_error(TNS_ERR_ARG, "image: net input %lld x %lld outside [1, %lld]",
+                     (long long)netW, (long long)netH, (long long)lim);
+  if (bytes ? (channels < 1 || channels > 4 || pixelStride < channels || pixelStride > lim)
+            : (channels < 1 || channels > 1024))
+    return set_error(TNS_ERR_ARG, "image: channels %lld (bytes: 1..4, floats: 1..1024) or pixel "
+                     "stride %lld", (long long)channels, (long long)pixelStride);
+  if (bytes && (tableKind < 0 || tableKind > 2))
+    return set_error(TNS_ERR_ARG, "image: table kind %d", (int)tableKind);
+  if (count == 0) return TNS_OK;
+  if (!src || !geom || !dst || (bytes && tableKind == 2 && !table))
+    return set_error(TNS_ERR_ARG, "image: null operand");
+  std::vector<ImageGeom> gs((size_t)count);
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t off = geom[4 * i], w = geom[4 * i + 1], h = geom[4 * i + 2], rs = geom[4 * i + 3];
+    if (off < 0 || w < 1 || w > lim || h < 1 || h > lim || rs < w * (bytes ? pixelStride : 1))
+      return set_error(TNS_ERR_ARG, "image %lld: offset %lld, %lld x %lld outside [1, %lld], or "
+                       "row stride %lld shorter than a row", (long long)i, (long long)off,
+                       (long long)w, (long long)h, (long long)lim, (long long)rs);
+    int64_t nw = netW, nh = netH;
+    if (letter) {
+      if (netW * h < netH * w)  // (aWidth / self.w) < (aHeight / self.h), exactly
+        nh = h * netW / w;
+      else
+        nw = w * netH / h;
+    }
+    if (nw < 2 || nh < 2)  // the reference divides by aWidth-1, aHeight-1
+      return set_error(TNS_ERR_ARG, "image %lld: resize target %lld x %lld below 2",
+                       (long long)i, (long long)nw, (long long)nh);
+    ImageGeom& g = gs[(size_t)i];
+    g.off = off, g.rs = rs, g.w = (int)w, g.h = (int)h, g.nw = (int)nw, g.nh = (int)nh;
+    g.dx = (int)((netW - nw) / 2), g.dy = (int)((netH - nh) / 2);
+    // integer / integer is a real, stored to a single: one rounding of the
+    // double quotient gives the same value for operands below 2^24
+    g.ws = (float)((double)(w - 1) / (double)(nw - 1));
+    g.hs = (float)((double)(h - 1) / (double)(nh - 1));
+  }
+  float tab[256] = {};
+  for (int b = 0; bytes && b < 256; ++b)
+    tab[b] = tableKind == 2   ? table[b]
+             : tableKind == 1 ? (float)((double)b / 255.0)              // p.r / $ff
+                              : (float)((double)(b * 257) / 65280.0);   // TFPColor word / $ff00
+  for (int64_t i = 0; placed && i < count; ++i) {
+    const ImageGeom& g = gs[(size_t)i];
+    placed[4 * i] = g.nw, placed[4 * i + 1] = g.nh, placed[4 * i + 2] = g.dx;
+    placed[4 * i + 3] = g.dy;
+  }
+  return hip_status(launch_image_to_input(bytes, gs.data(), count, src, (int)channels,
+                                          (int)pixelStride, tab, (int)netW, (int)netH, dst,
+                                          c->stream),
+                    "image to input");
+}
+}  // namespace
+
+int tns_image_bytes_to_input(tns_ctx* c, int64_t count, const uint8_t* src, const int64_t* geom,
+                             int64_t channels, int64_t pixelStride, int32_t tableKind,
+                             const float* table, int64_t netW, int64_t netH, int32_t letter,
+                             float* dst, int64_t* placed) {
+  return image_to_input(c, true, count, src, geom, channels, pixelStride, tableKind, table, netW,
+                        netH, letter, dst, placed);
+}
+
+int tns_image_floats_to_input(tns_ctx* c, int64_t count, const float* src, const int64_t* geom,
+                              int64_t channels, int64_t netW, int64_t netH, int32_t letter,
+                              float* dst, int64_t* placed) {
+  return image_to_input(c, false, count, src, geom, channels, 1, 0, nullptr, netW, netH, letter,
+                        dst, placed);
+}
+
 // TNNCuda.forwardMaxPool / backwardMaxPool (nncuda.pas:132-133) and the local
 // average pool over the same geometry
 namespace {

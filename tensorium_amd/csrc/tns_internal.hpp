@@ -385,6 +385,22 @@ hipError_t launch_yolo_detections(const DetParams& p, const float* out, int64_t*
 hipError_t launch_nms_sort(int batch, int capacity, int classes, const int64_t* counts,
                            const float* boxes, const float* objectness, float* probs,
                            float thresh, hipStream_t s);
+// image.hip: TImageData.resize / letterBox of `count` images into dst
+// [count][channels][netH][netW].  One image's geometry, worked out on the
+// host: its first element from src (bytes or floats), row stride, extent, the
+// resize target nw x nh, where that sits in the net input (dx, dy; the rest is
+// 0.5), and the two scale factors as the singles the reference stores.
+// kImagePerLaunch images' geometry travel as one launch's kernel arguments.
+constexpr int kImagePerLaunch = 32;
+constexpr int64_t kImageMaxExtent = 32768;
+struct ImageGeom {
+  int64_t off, rs;
+  int w, h, nw, nh, dx, dy;
+  float ws, hs;
+};
+hipError_t launch_image_to_input(bool bytes, const ImageGeom* geom, int64_t count, const void* src,
+                                 int channels, int pixelStride, const float* table, int netW,
+                                 int netH, float* dst, hipStream_t s);
 hipError_t launch_bias_activate(float* dst, int64_t nFilters, int64_t blockSize,
                                 const float* bias, int64_t batch, int act, hipStream_t s);
 hipError_t launch_derive(const float* x, int64_t n, int act, float* delta, hipStream_t s);

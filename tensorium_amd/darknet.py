@@ -1182,6 +1182,93 @@ def detection_rows_to_host(torch, taken, cap, classes, boxes, obj, probs, pin=No
     return res, pin
 
 
+@dataclass
+class Placement:
+    """Where ``images_to_input`` put one image: the resize target new_w x
+    new_h at (dx, dy) of the net input, the source's extent, and
+    letterBoxEx's ratio (None without ``letter``)."""
+    new_w: int
+    new_h: int
+    dx: int
+    dy: int
+    w: int
+    h: int
+    ratio: object = None
+
+
+def images_to_input(hip, torch, images, channels, net_w, net_h, dst, letter=False, table="fpc"):
+    """TImageData.resize, or with ``letter`` letterBoxEx (ntypes.pas:837-947),
+    of every image into dst [len(images), channels, net_h, net_w] on the
+    device (TNNHip.imageToInput, one launch).  ``images``: uint8 [h, w, c]
+    arrays (interleaved, as decoders deliver them; c >= channels, the first
+    ``channels`` of a pixel are taken) or float32 [channels, h, w] arrays
+    (TImageData's layout), NumPy or device tensors, all of one kind, of
+    differing sizes.  Host images cross as their own bytes in one copy.
+    Returns a Placement per image."""
+    if not images:
+        return []
+    on_dev = [hasattr(im, "is_cuda") for im in images]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("images: NumPy arrays and tensors in one call")
+    kinds = {str(im.dtype).replace("torch.", "") for im in images}
+    if len(kinds) != 1 or kinds & {"uint8", "float32"} != kinds:
+        raise ValueError(f"images: one of uint8 / float32 for all of them, got {sorted(kinds)}")
+    as_bytes = kinds == {"uint8"}
+    geom, at, ps = [], 0, None
+    for n, im in enumerate(images):
+        if im.ndim != 3:
+            raise ValueError(f"image {n}: shape {tuple(im.shape)}")
+        h, w, c = im.shape if as_bytes else (im.shape[1], im.shape[2], im.shape[0])
+        if (c < channels or c > 4) if as_bytes else c != channels:
+            raise ValueError(f"image {n}: {c} channels for a network of {channels}")
+        if as_bytes and ps not in (None, c):
+            raise ValueError(f"image {n}: {c} bytes a pixel after images of {ps}")
+        ps = c
+        geom.append((at, w, h, w * c if as_bytes else w))
+        at += h * w * c
+    if all(on_dev):
+        src = torch.cat([im.contiguous().reshape(-1) for im in images])
+    else:
+        src = torch.from_numpy(np.concatenate(
+            [np.ascontiguousarray(im).reshape(-1) for im in images])).cuda()
+    placed = hip.imageToInput(src, geom, channels, net_w, net_h, dst, letter=letter, table=table,
+                              pixelStride=ps if as_bytes else None)
+    res = []
+    for (nw, nh, dx, dy), (_, w, h, _) in zip(placed, geom):
+        ratio = None
+        if letter:  # letterBoxEx: aWidth / self.w or aHeight / self.h, a real stored to a single
+            ratio = np.float32(net_w / w) if net_w * h < net_h * w else np.float32(net_h / h)
+        res.append(Placement(nw, nh, dx, dy, w, h, ratio))
+    return res
+
+
+def letterbox_truth(boxes, placements, net_w, net_h, max_boxes):
+    """loadVOCBatch's truth rows (Samples/FPC/MSCOCO_Yolo/MSCOCOYolo.pas:
+    461-480) for images letterboxed by ``images_to_input(letter=True)``:
+    ``boxes[b]`` is image b's objects in file order, each (xmin, ymin, xmax,
+    ymax, class) in source pixels, or None for one the sample skips
+    (`difficult`), whose row stays zero.  left = dx + trunc(single(xmin) *
+    ratio) and so on, then x = (left+right) / (2*netW), y likewise, w =
+    (right-left) / netW, h likewise: integer quotients, reals stored to
+    singles.  Returns float32 [len(boxes), max_boxes, 6] rows x, y, w, h,
+    class, 0, zero after the last.  More than ``max_boxes`` objects are
+    refused (the sample's loop admits one more and writes it into the next
+    image's rows)."""
+    F = np.float32
+    out = np.zeros((len(boxes), max_boxes, 6), F)
+    for b, (objs, p) in enumerate(zip(boxes, placements)):
+        if len(objs) > max_boxes:
+            raise ValueError(f"image {b}: {len(objs)} objects, max_boxes {max_boxes}")
+        for j, o in enumerate(objs):
+            if o is None:
+                continue
+            left, top, right, bottom = (d + int(np.trunc(F(v) * p.ratio))
+                                        for d, v in zip((p.dx, p.dy, p.dx, p.dy), o[:4]))
+            out[b, j] = (F((left + right) / (2 * net_w)), F((top + bottom) / (2 * net_h)),
+                         F((right - left) / net_w), F((bottom - top) / net_h), F(o[4]), 0)
+    return out
+
+
 class HipDarknet(_RnnLayers, _LstmLayers):
     """TNNet.forward over a darknet layer plan on the HIP backend (nnet.pas:
     275-310 selects forwardGPU per layer): every layer's output stays in a
@@ -1340,6 +1427,41 @@ class HipDarknet(_RnnLayers, _LstmLayers):
                                                     getattr(self, "_det_pin", None))
         return res
 
+    def load_images(self, images, letter=False, table="fpc"):
+        """The batch's images (``images_to_input``: uint8 [h, w, c] or float32
+        [c, h, w], NumPy or device, of differing sizes) resized to the net
+        input as the sample does before ``predict`` (MSCOCOYolo.pas:348-358),
+        or letterboxed with ``letter``, on the device.  Returns the [batch, c,
+        h, w] device input, a buffer this object keeps and the next call
+        overwrites, and a Placement per image."""
+        net = self.net
+        if len(images) != net.batch:
+            raise ValueError(f"{len(images)} images for a batch of {net.batch}")
+        if getattr(self, "_input", None) is None:
+            self._input = self.torch.empty((net.batch, net.c, net.h, net.w), device="cuda")
+        placed = images_to_input(self.hip, self.torch, images, net.c, net.w, net.h, self._input,
+                                 letter=letter, table=table)
+        return self._input, placed
+
+    def detect_images(self, images, thresh=0.5, nms=None, letter=False, relative=True,
+                      table="fpc"):
+        """``load_images`` -> ``forward`` -> ``detections``: decoded images in,
+        per image (boxes, objectness, probs) out.  ``detections`` corrects the
+        boxes by one image extent for the whole batch, and with ``letter`` or
+        without ``relative`` the boxes depend on it, so images of differing
+        sizes are then refused; the sample's mode (resize, relative) takes
+        them mixed."""
+        x, placed = self.load_images(images, letter=letter, table=table)
+        sizes = {(p.w, p.h) for p in placed}
+        if len(sizes) > 1 and (letter or not relative):
+            raise ValueError("detect_images: images of differing sizes "
+                             f"{sorted(sizes)} with letter=True or relative=False: the boxes' "
+                             "correction takes one image extent for the whole batch")
+        self.forward(x)
+        im_w, im_h = (placed[0].w, placed[0].h)
+        return self.detections(im_w, im_h, thresh=thresh, relative=relative, letter=letter,
+                               nms=nms)
+
 
 class HipDarknetTrain(_RnnLayers, _LstmLayers):
     """One training pass of a darknet network on the HIP backend, in the
@@ -1480,6 +1602,29 @@ class HipDarknetTrain(_RnnLayers, _LstmLayers):
             self.conv[l.index] = st
             ws = max(ws, B * l.c * l.size * l.size * l.out_h * l.out_w)
         self.ws = torch.empty(ws, device=dev)
+
+    def load_batch(self, images, boxes, table="fpc"):
+        """loadVOCBatch (MSCOCOYolo.pas:432-484) without the files: every
+        image letterboxed into the net input on the device
+        (``images_to_input(letter=True)``) and its objects' pixel boxes
+        mapped into it (``letterbox_truth``; ``boxes[b]``: (xmin, ymin, xmax,
+        ymax, class) per object).  Returns the device input [batch, c, h, w],
+        kept by this object and overwritten by the next call, and the device
+        truth [batch, max_boxes*6] that ``forward`` takes under
+        ``yolo_loss``."""
+        net, torch = self.net, self.torch
+        yolos = [l for l in net.layers if l.kind == "yolo"]
+        if not yolos:
+            raise ValueError("load_batch: the network has no [yolo] layer")
+        if len(images) != net.batch or len(boxes) != net.batch:
+            raise ValueError(f"{len(images)} images and {len(boxes)} box lists for a batch of "
+                             f"{net.batch}")
+        if getattr(self, "_input", None) is None:
+            self._input = torch.empty((net.batch, net.c, net.h, net.w), device="cuda")
+        placed = images_to_input(self.hip, torch, images, net.c, net.w, net.h, self._input,
+                                 letter=True, table=table)
+        rows = letterbox_truth(boxes, placed, net.w, net.h, yolos[0].max_boxes)
+        return self._input, torch.from_numpy(rows.reshape(net.batch, -1)).cuda()
 
     def forward(self, x, truth=None, seeds=None):
         """TNet.forward with state.isTraining (BN statistics of the batch,

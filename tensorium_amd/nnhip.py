@@ -353,6 +353,44 @@ class TNNHip:
                                         _ptr(boxes), _ptr(objectness), _ptr(probs),
                                         float(thresh)))
 
+    IMAGE_TABLES = {"fpc": 0, "255": 1}
+
+    def imageToInput(self, src, geom, channels, netW, netH, dst, letter=False, table="fpc",
+                     pixelStride=None):
+        """TImageData.resize, or with ``letter`` letterBox / letterBoxEx, of
+        len(geom) images into dst [count][channels][netH][netW], one launch
+        (tns_image_bytes_to_input / tns_image_floats_to_input).  src: a
+        device uint8 tensor (interleaved pixels, ``pixelStride`` bytes each,
+        default ``channels``) or float32 tensor (planar); geom: per image
+        (offset, w, h, rowStride), offset and rowStride in src's elements;
+        table, for bytes: "fpc" (b*257/65280), "255" (b/255) or 256 floats.
+        Returns per image (new_w, new_h, dx, dy)."""
+        count = len(geom)
+        g = (C.c_int64 * max(4 * count, 1))(*[int(v) for row in geom for v in row])
+        placed = (C.c_int64 * max(4 * count, 1))()
+        if src is not None and torch is not None and isinstance(src, torch.Tensor) \
+                and src.dtype == torch.uint8:
+            if not src.is_cuda or not src.is_contiguous():
+                raise TnsError("TNNHip expects contiguous device (cuda) tensors")
+            if isinstance(table, str):
+                if table not in self.IMAGE_TABLES:
+                    raise TnsError(f"imageToInput: table {table!r} (fpc, 255 or 256 floats)")
+                kind, tab = self.IMAGE_TABLES[table], None
+            else:
+                vals = [float(v) for v in table]
+                if len(vals) != 256:
+                    raise TnsError(f"imageToInput: a table of {len(vals)} entries")
+                kind, tab = 2, (C.c_float * 256)(*vals)
+            check(self.lib.tns_image_bytes_to_input(
+                self.ctx, count, src.data_ptr(), g, channels,
+                channels if pixelStride is None else pixelStride, kind, tab, netW, netH,
+                int(bool(letter)), _ptr(dst), placed))
+        else:
+            check(self.lib.tns_image_floats_to_input(
+                self.ctx, count, _ptr(src), g, channels, netW, netH, int(bool(letter)), _ptr(dst),
+                placed))
+        return [tuple(placed[4 * i:4 * i + 4]) for i in range(count)]
+
     # -- layer drivers ------------------------------------------------------------
     def conv2d(self, batch, C_, H, W, input, weights, filters, kH, kW, wPadding, hPadding,
                xStride, yStride, xDilation, yDilation, workspace, out):
