@@ -841,6 +841,27 @@ int tns_hip_gemm_variant(tns_ctx* ctx, int32_t variant, uint8_t transA, uint8_t 
                          const float* B, int64_t bOffset, int64_t ldb, int64_t strideB,
                          float BETA, float* C, int64_t cOffset, int64_t ldc, int64_t strideC,
                          int64_t batchCount);
+/* Which kernel a GEMM would run on, without running it (no context, no device
+ * call: the dispatch is a pure function of these numbers).  `variant` as
+ * tns_hip_gemm_variant; `in` holds TNS_GP_COUNT values indexed by TNS_GP_*
+ * (the shape as tns_hip_gemm_strided_batched takes it; ALPHA == 1 or not; the
+ * beta mode: 0 C not read, 1 BETA == 1, 2 BETA * C; the epilogue: 0 none;
+ * whether A and B are 16-byte aligned; the options TNS_OPT_NT_SDOT,
+ * TNS_OPT_TT_EXACT and TNS_OPT_SDOT_FORM).  Writes one JSON object into `out`
+ * (out_len bytes, 512 are enough): err (0, or TNS_ERR_UNSUPPORTED where the
+ * forced variant refuses the problem, msg saying why), family (empty, tile,
+ * nn_big, nt_sdot, sdot_chains, sdot_rc, tt), form and name within the family,
+ * leaf (the kernel instantiation, one of tns_gemm_plan_leaf_name), and the
+ * template choices: vec_a / vec_b (staging widths 4 or 1), rows / pre / alpha1
+ * (large-NN forms 6..8), tn / vec / bk / o32 (the sdot-order MFMA kernel). */
+enum { TNS_GP_TRANS_A = 0, TNS_GP_TRANS_B = 1, TNS_GP_M = 2, TNS_GP_N = 3, TNS_GP_K = 4,
+       TNS_GP_LDA = 5, TNS_GP_LDB = 6, TNS_GP_LDC = 7, TNS_GP_STRIDE_A = 8, TNS_GP_STRIDE_B = 9,
+       TNS_GP_STRIDE_C = 10, TNS_GP_BATCH = 11, TNS_GP_ALPHA_IS_ONE = 12, TNS_GP_BETA_MODE = 13,
+       TNS_GP_EPI = 14, TNS_GP_A_ALIGNED16 = 15, TNS_GP_B_ALIGNED16 = 16, TNS_GP_NT_SDOT = 17,
+       TNS_GP_TT_EXACT = 18, TNS_GP_SDOT_FORM = 19, TNS_GP_COUNT = 20 };
+int         tns_gemm_plan(int32_t variant, const int64_t* in, char* out, int64_t out_len);
+int         tns_gemm_plan_leaf_count(void);
+const char* tns_gemm_plan_leaf_name(int32_t leaf);
 
 /* TNS_OPT_STRICT_BETA0 (default 1): beta==0 computes 0*C like the reference
  * (NaN/Inf in C propagate).  0 = BLAS convention (C not read).

@@ -350,6 +350,12 @@ function tns_hip_gemm_variant(ctx: PTnsCtx; variant: longint; transA, transB: bo
   M, N, K: int64; ALPHA: single; A: THipMem; aOffset, lda, strideA: int64; B: THipMem; bOffset,
   ldb, strideB: int64; BETA: single; C: THipMem; cOffset, ldc, strideC, batchCount: int64): longint;
   cdecl; external libtns;
+{ which kernel a GEMM would run on (no device call): shape = TNS_GP_COUNT
+  int64 values indexed by TNS_GP_* of tns.h, buf receives one JSON object }
+function tns_gemm_plan(variant: longint; shape: PInt64; buf: PAnsiChar;
+  out_len: int64): longint; cdecl; external libtns;
+function tns_gemm_plan_leaf_count(): longint; cdecl; external libtns;
+function tns_gemm_plan_leaf_name(leaf: longint): PAnsiChar; cdecl; external libtns;
 function tns_set_option(opt: longint; value: int64): longint; cdecl; external libtns;
 
 type

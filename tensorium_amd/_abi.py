@@ -123,6 +123,10 @@ PROTOTYPES: dict[str, tuple] = {
     "tns_hip_gemm_variant": (C.c_int, [vp, i32, u8, u8, i64, i64, i64, f32, fptr, i64, i64, i64,
                                        fptr, i64, i64, i64, f32, fptr, i64, i64, i64, i64]),
     "tns_hip_op_ms": (C.c_double, [vp, i32]),
+    # the GEMM dispatch as a pure function: TNS_GP_COUNT int64 in, JSON out
+    "tns_gemm_plan": (C.c_int, [i32, C.POINTER(i64), C.c_char_p, i64]),
+    "tns_gemm_plan_leaf_count": (C.c_int, []),
+    "tns_gemm_plan_leaf_name": (C.c_char_p, [i32]),
 }
 
 
@@ -169,6 +173,30 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+# tns_gemm_plan's input, in TNS_GP_* order (include/tns.h)
+GEMM_PLAN_FIELDS = ("transA", "transB", "M", "N", "K", "lda", "ldb", "ldc", "strideA", "strideB",
+                    "strideC", "batch", "alpha1", "beta_mode", "epi", "a16", "b16", "nt_sdot",
+                    "tt_exact", "sdot_form")
+_GEMM_PLAN_DEFAULTS = dict(strideA=0, strideB=0, strideC=0, batch=1, alpha1=1, beta_mode=2, epi=0,
+                           a16=1, b16=1, nt_sdot=1, tt_exact=1, sdot_form=-1)
+
+
+def gemm_plan(variant: int = -1, **shape) -> dict:
+    """The plan tns_gemm_plan gives (a dict; no GPU needed).  transA, transB,
+    M, N, K are required; lda / ldb / ldc default to the packed row lengths,
+    the rest to one image, ALPHA = 1, BETA scaled, aligned operands and the
+    default options."""
+    import json
+    v = dict(_GEMM_PLAN_DEFAULTS, **shape)
+    v.setdefault("lda", v["M"] if v["transA"] else v["K"])
+    v.setdefault("ldb", v["K"] if v["transB"] else v["N"])
+    v.setdefault("ldc", v["N"])
+    arr = (i64 * len(GEMM_PLAN_FIELDS))(*(int(v[k]) for k in GEMM_PLAN_FIELDS))
+    buf = C.create_string_buffer(1024)
+    check(load().tns_gemm_plan(int(variant), arr, buf, len(buf)))
+    return json.loads(buf.value.decode())
 
 
 def check(rc: int) -> None:

@@ -542,7 +542,7 @@ hipError_t launch_full(const GemmArgs& a, bool ta, bool tb, bool av, bool bv, hi
 // all transposes, float4 operands only (large-GEMM production shape)
 template <class S>
 hipError_t launch_trans4(const GemmArgs& a, bool ta, bool tb, bool av, bool bv, hipStream_t s) {
-  if (!av || !bv) return hipErrorInvalidValue;
+  if (!tile_kind_supports(KIND_launch_trans4, ta, tb, av, bv)) return hipErrorInvalidValue;
   if (!ta && !tb) return launch_variant<S, false, false, 4, 4>(a, s);
   if (!ta && tb) return launch_variant<S, false, true, 4, 4>(a, s);
   if (ta && !tb) return launch_variant<S, true, false, 4, 4>(a, s);
@@ -564,7 +564,7 @@ hipError_t launch_conv(const GemmArgs& a, bool av, hipStream_t s) {
 // experimental tile shapes: NN with float4 operands only
 template <class S>
 hipError_t launch_nn4(const GemmArgs& a, bool ta, bool tb, bool av, bool bv, hipStream_t s) {
-  if (ta || tb || !av || !bv) return hipErrorInvalidValue;
+  if (!tile_kind_supports(KIND_launch_nn4, ta, tb, av, bv)) return hipErrorInvalidValue;
   return launch_variant<S, false, false, 4, 4>(a, s);
 }
 
@@ -600,31 +600,7 @@ using S64x64w8m16 = Shape<64, 64, 32, 2, 4, 2, 2, 16>;
 
 // one launcher per shape, defined in the sgemm_*.hip translation units
 typedef hipError_t (*ShapeLauncher)(const GemmArgs&, bool, bool, bool, bool, hipStream_t);
-#define TNS_SHAPES(X)                                    \
-  X(128x128, "128x128x32_w2x2", 128, 128, launch_full)   \
-  X(128x64, "128x64x32_w2x2", 128, 64, launch_full)      \
-  X(64x128, "64x128x32_w2x2", 64, 128, launch_full)      \
-  X(64x256, "64x256x32_w1x4", 64, 256, launch_full)      \
-  X(32x256, "32x256x32_w1x4", 32, 256, launch_full)      \
-  X(256x256w8, "256x256x32_w2x4", 256, 256, launch_trans4) \
-  X(64x64, "64x64x32_w2x2", 64, 64, launch_full)          \
-  X(256x256, "256x256x32_w2x2", 256, 256, launch_nn4)    \
-  X(256x256k16, "256x256x16_w2x2", 256, 256, launch_nn4) \
-  X(256x128, "256x128x32_w2x2", 256, 128, launch_nn4)    \
-  X(128x256, "128x256x32_w2x2", 128, 256, launch_nn4)    \
-  X(256x128k16, "256x128x16_w2x2", 256, 128, launch_nn4) \
-  X(64x64m16, "64x64x32_w2x2_m16", 64, 64, launch_full)  \
-  X(32x32m16, "32x32x32_w2x2_m16", 32, 32, launch_full)  \
-  X(64x32m16, "64x32x32_w2x2_m16", 64, 32, launch_nn4)   \
-  X(32x64m16, "32x64x32_w2x2_m16", 32, 64, launch_nn4)   \
-  X(128x128m16, "128x128x32_w2x2_m16", 128, 128, launch_nn4) \
-  X(256x256w8m16, "256x256x32_w2x4_m16", 256, 256, launch_trans4) \
-  X(128x64w8, "128x64x32_w4x2", 128, 64, launch_nn4)     \
-  X(64x128w8, "64x128x32_w2x4", 64, 128, launch_nn4)     \
-  X(128x128w8, "128x128x32_w4x2", 128, 128, launch_nn4)  \
-  X(64x64d1, "64x64x32_w2x2_d1", 64, 64, launch_nn4)     \
-  X(64x64w8m16, "64x64x32_w2x4_m16", 64, 64, launch_nn4)
-
+// (the table of shapes, TNS_SHAPES: gemm_plan.hpp)
 #define TNS_DECL(ID, NAME, BMv, BNv, KIND) \
   hipError_t launch_shape_##ID(const GemmArgs&, bool, bool, bool, bool, hipStream_t);
 TNS_SHAPES(TNS_DECL)

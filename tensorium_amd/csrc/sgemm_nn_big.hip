@@ -281,8 +281,6 @@ __global__ __launch_bounds__(G::NT, G::MINB_) void sgemm_nn_big_kernel(GemmArgs 
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 using G256 = Geo<256, 256, 2, 4, 1>;  // 8 waves, wave tile 128x64, 1 block/CU
 using G128 = Geo<128, 128, 2, 2, 2>;  // 4 waves, wave tile 64x64, 2 blocks/CU
 using G256x128 = Geo<256, 128, 2, 2, 1>;  // 4 waves, wave tile 128x64
@@ -291,18 +289,18 @@ using G256w16 = Geo<256, 256, 4, 4, 1>;   // 16 waves, wave tile 64x64, 4 waves 
 // LDS), so one block's barrier and staging are covered by the other's MFMAs
 using G256x128k16 = Geo<256, 128, 2, 2, 2, 16>;
 
+// (which problems a form takes: nn_big_applies, gemm_plan.cpp, over the tile
+// sizes of kNnBigGeo)
 template <class G>
-bool applies(const GemmArgs& a) {
-  if (a.conv || a.epi != EPI_NONE || a.beta_mode == BETA_STORE) return false;
-  if (a.M % G::BM_ || a.N % G::BN_ || a.K % G::BK_ || a.M <= 0 || a.N <= 0) return false;
-  if (a.lda % 4 || a.ldb % 4 || !aligned16(a.A) || !aligned16(a.B)) return false;
-  if (a.batch > 1 && (a.strideA % 4 || a.strideB % 4)) return false;
-  return (a.M / G::BM_) * (a.N / G::BN_) <= 0x7fffffff;
+constexpr bool geo_is(int form) {
+  return G::BM_ == kNnBigGeo[form].bm && G::BN_ == kNnBigGeo[form].bn &&
+         G::BK_ == kNnBigGeo[form].bk && !kNnBigGeo[form].off32;
 }
+static_assert(geo_is<G256>(0) && geo_is<G128>(1) && geo_is<G256x128>(2) && geo_is<G256w16>(3) &&
+              geo_is<G256x128k16>(4), "kNnBigGeo lists these tiles");
 
 template <class G>
 hipError_t launch(const GemmArgs& a, hipStream_t s) {
-  if (!applies<G>(a)) return hipErrorInvalidValue;
   const int64_t tiles = (a.M / G::BM_) * (a.N / G::BN_);
   for (int64_t b0 = 0; b0 < a.batch; b0 += 65535) {
     GemmArgs sub = a;
@@ -330,7 +328,7 @@ hipError_t launch(const GemmArgs& a, hipStream_t s) {
 // for every K, both with the flat loop's fragment addresses held in
 // registers; form 8 the rows schedule with the per-step address arithmetic
 // the kernel had before, kept for A/B (the flat one below K = 128))
-int sgemm_nn_big_count() { return 9; }
+int sgemm_nn_big_count() { return kNnBigForms; }
 const char* sgemm_nn_big_name(int v) {
   static const char* names[] = {"256x256x32_w2x4_nn_big", "128x128x32_w2x2_nn_big",
                                 "256x128x32_w2x2_nn_big", "256x256x32_w4x4_nn_big",
@@ -340,35 +338,20 @@ const char* sgemm_nn_big_name(int v) {
   return v >= 0 && v < sgemm_nn_big_count() ? names[v] : "";
 }
 
-// heuristic: the 256x256 tile when it gives about a block per CU, at one
-// wave per SIMD with LDS-DMA operands where it applies (form 6; 4096^3 0.983
-// -> 0.950 ms against the ping-pong form 5, which itself took 0.994 -> 0.972
-// from form 0; all bit-identical).  Form 6 runs its row-ordered schedule
-// wherever K >= 128 and the flat one (form 7) below: rows measured faster
-// than flat by more than flat's round-to-round spread at every K (128 ..
-// 4096) and beta mode tried (4096^3 0.9545 -> 0.9393 ms, 1024 x 1024^3 16.37
-// -> 16.09; profiles/sgemm_w4_rows_ab.json), so no shape picks form 7.  From
-// K = 256 on form 6 holds its loop's fragment addresses in registers (4096^3
-// 0.9364 -> 0.9167 ms against form 8, which computes them per step; K = 128
-// measured slower that way and 160 .. 384 level, so below 256 form 6 is form
-// 8's kernel; profiles/sgemm_w4_afrag_ab.json)
-int sgemm_nn_big_pick(const GemmArgs& a) {
-  if (applies<G256>(a) && (a.M / 256) * (a.N / 256) * a.batch >= 192)
-    return sgemm_nn_w4_applies(a) ? 6 : sgemm_nn_pp_applies(a) ? 5 : 0;
-  return -1;
-}
-
-hipError_t launch_sgemm_nn_big(int v, const GemmArgs& a, hipStream_t s) {
-  switch (v) {
+// (the heuristic, nn_big_pick, and the w4 kernel's template choices: gemm_plan.cpp)
+// the plan says the form applies (plan_gemm_variant asks nn_big_applies)
+hipError_t launch_sgemm_nn_big(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  if (p.err || p.family != GEMM_NN_BIG) return hipErrorInvalidValue;
+  // (interior-only addressing: never run a plan made for another problem)
+  if (!nn_big_applies(p.form, gemm_shape(a, false, false))) return hipErrorInvalidValue;
+  switch (p.form) {
     case 0: return launch<G256>(a, s);
     case 1: return launch<G128>(a, s);
     case 2: return launch<G256x128>(a, s);
     case 3: return launch<G256w16>(a, s);
     case 4: return launch<G256x128k16>(a, s);
     case 5: return launch_sgemm_nn_pp(a, s);
-    case 6: return launch_sgemm_nn_w4(a, s, true);
-    case 7: return launch_sgemm_nn_w4(a, s, false);
-    case 8: return launch_sgemm_nn_w4(a, s, true, false);  // the parent's fragment addressing
+    case 6: case 7: case 8: return launch_sgemm_nn_w4(p, a, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -250,20 +250,13 @@ __global__ __launch_bounds__(NT, 1) void sgemm_nn_pp_kernel(GemmArgs p) {
     }
 }
 
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
-bool sgemm_nn_pp_applies(const GemmArgs& a) {
-  if (a.conv || a.epi != EPI_NONE || a.beta_mode == BETA_STORE) return false;
-  if (a.M % BM || a.N % BN || a.K % BK || a.M <= 0 || a.N <= 0) return false;
-  if (a.lda % 4 || a.ldb % 4 || !aligned16(a.A) || !aligned16(a.B)) return false;
-  if (a.batch > 1 && (a.strideA % 4 || a.strideB % 4)) return false;
-  return (a.M / BM) * (a.N / BN) <= 0x7fffffff;
-}
+static_assert(BM == kNnBigGeo[5].bm && BN == kNnBigGeo[5].bn && BK == kNnBigGeo[5].bk &&
+              !kNnBigGeo[5].off32, "form 5 of kNnBigGeo is this tile");
 
+// (the caller's plan says the form applies: nn_big_applies(5, .), gemm_plan.cpp)
 hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s) {
-  if (!sgemm_nn_pp_applies(a)) return hipErrorInvalidValue;
   const int64_t tiles = (a.M / BM) * (a.N / BN);
   for (int64_t b0 = 0; b0 < a.batch; b0 += 65535) {
     GemmArgs sub = a;

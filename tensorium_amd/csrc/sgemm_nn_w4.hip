@@ -116,11 +116,11 @@ typedef const __attribute__((address_space(3))) floatx4* lds_cptr4;
 
 constexpr int BM = 256, BN = 256, BK = 32, NT = 256;
 constexpr int A_TILE = BM * BK, B_TILE = BK * BN, STAGE = A_TILE + B_TILE;  // floats
-constexpr int ROWS_MIN_TILES = 4;  // the rows schedule's two ends are two k-tiles each
+constexpr int ROWS_MIN_TILES = kW4RowsMinTiles;  // the rows schedule's two ends are two k-tiles each
 // the picked (rows) form holds its loop's fragment addresses in registers from
 // this many k-tiles on: measured slower below (K = 128, no regular tile, by
 // 0.5 us), level from 160 to 384, faster from 512
-constexpr int PRE_MIN_TILES = 8;
+constexpr int PRE_MIN_TILES = kW4PreMinTiles;
 
 __device__ __forceinline__ void dma16(const float* sbase, unsigned voff, unsigned lds) {
   unsigned keep;
@@ -692,36 +692,26 @@ __global__ __launch_bounds__(NT, 1) void sgemm_nn_w4_kernel(GemmArgs p) {
 #endif
 }
 
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 #ifdef TNS_W4_STAMPS
 unsigned* g_w4_stamps = nullptr;
 #endif
 
 }  // namespace
 
-bool sgemm_nn_w4_applies(const GemmArgs& a) {
-  if (a.conv || a.epi != EPI_NONE || a.beta_mode == BETA_STORE) return false;
-  if (a.M % BM || a.N % BN || a.K % BK || a.M <= 0 || a.N <= 0) return false;
-  if (a.lda % 4 || a.ldb % 4 || !aligned16(a.A) || !aligned16(a.B)) return false;
-  if (a.batch > 1 && (a.strideA % 4 || a.strideB % 4)) return false;
-  // (32-bit byte offsets: 7 rows of A per DMA lane offset, a block's 256
-  // rows of C from its first row)
-  if (a.lda * 4 * 8 > 0x7fffffffLL || (256 * a.ldc + a.N) * 4 > 0x7fffffffLL) return false;
-  return (a.M / BM) * (a.N / BN) <= 0x7fffffff;
-}
+static_assert(BM == kNnBigGeo[6].bm && BN == kNnBigGeo[6].bn && BK == kNnBigGeo[6].bk &&
+              kNnBigGeo[6].off32, "forms 6..8 of kNnBigGeo are this tile");
 
+// the plan (plan_gemm_variant, gemm_plan.cpp) says the form applies and gives
+// the kernel's template arguments:
 // rows: the row-ordered schedule of the first and last two k-tiles where K
 // has them (K >= 128), the flat schedule below that
 // pre: the flat loop reads its fragments from addresses held in registers
 // (the kernel's PRE; with rows only where K >= 256, see PRE_MIN_TILES); false
 // keeps the per-step address arithmetic, for A/B
-hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows, bool pre) {
-  if (!sgemm_nn_w4_applies(a)) return hipErrorInvalidValue;
+hipError_t launch_sgemm_nn_w4(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  if (p.err || p.family != GEMM_NN_BIG || p.form < 6) return hipErrorInvalidValue;
+  const bool rows = p.rows, pre = p.pre, alpha1 = p.alpha1;
   const int64_t tiles = (a.M / BM) * (a.N / BN);
-  const bool alpha1 = a.alpha == 1.0f;
-  pre = pre && (!rows || a.K / BK >= PRE_MIN_TILES);
-  rows = rows && a.K / BK >= ROWS_MIN_TILES;
   for (int64_t b0 = 0; b0 < a.batch; b0 += 65535) {
     GemmArgs sub = a;
     const int64_t nb = a.batch - b0 < 65535 ? a.batch - b0 : 65535;

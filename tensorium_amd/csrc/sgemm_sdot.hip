@@ -255,53 +255,32 @@ hipError_t launch_tn(const GemmArgs& a, hipStream_t s) {
   return hipSuccess;
 }
 
-bool k_vec4(const float* p, int64_t ld, int64_t stride, int64_t batch, int64_t K) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
-  if (ld % 4 != 0 || K % 4 != 0) return false;
-  return batch <= 1 || stride % 4 == 0;
-}
-
 }  // namespace
 
 static int g_sdot_form = -1;
 void set_sdot_form(int form) { g_sdot_form = form < 0 ? -1 : form; }
 
-// MFMA: 32x64 tiles when they still give >= 4 blocks per CU, else 32x32;
-// few outputs over a long k go to the VALU chain kernel
-hipError_t launch_sgemm_nt_sdot(const GemmArgs& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return hipSuccess;
-  if (g_sdot_form >= SDOT_FORM_RC) return launch_sdot_rc(g_sdot_form - SDOT_FORM_RC, a, s);
-  if (g_sdot_form > 0) return launch_sdot_chains(a, g_sdot_form - 1, s);
-  // few outputs over a long k (conv dW of the 416/208/104-pixel YOLOv3
-  // layers): the VALU chain kernel, tile by output count (scripts/
-  // sdot_forms.py, profiles/r02_sdot_forms.json: YOLOv3 layer 0 dW at batch
-  // 8 1.44 -> 0.28 ms, layer 2 0.35 -> 0.10 ms, layer 5 0.089 -> 0.056 ms;
-  // the 104^2 1x1 layers' 65536 outputs on four residues a lane, 0.130 ->
-  // 0.115 ms a call, profiles/r04_bwd_dw_sweep.json)
-  const int64_t t32 = ((a.M + 31) / 32) * ((a.N + 31) / 32) * a.batch;
-  if (g_sdot_form < 0 && a.K >= 4096 && t32 <= 64) {
-    const int64_t outs = a.M * a.N * a.batch;
-    return launch_sdot_chains(a, outs <= 8192 ? 1 : (outs <= 32768 ? 2 : 6), s);
+int get_sdot_form() { return g_sdot_form; }
+
+// launch_tn<p.tn, p.vec, p.bk, p.o32>, the seven instantiations
+// plan_gemm_nt_sdot names
+hipError_t launch_sgemm_nt_sdot_tn(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  if (p.err || p.family != GEMM_NT_SDOT) return hipErrorInvalidValue;
+  switch (p.form) {
+    case 0: return launch_tn<2, 4>(a, s);
+    case 1: return launch_tn<2, 1, 64, true>(a, s);
+    case 2: return launch_tn<2, 1>(a, s);
+    case 3: return launch_tn<1, 4, 256>(a, s);
+    case 4: return launch_tn<1, 1, 256>(a, s);
+    case 5: return launch_tn<1, 4>(a, s);
+    case 6: return launch_tn<1, 1>(a, s);
+    default: return hipErrorInvalidValue;
   }
-  // many 64x64 tiles over a short k (conv dW of the 26^2 / 13^2 layers, k =
-  // pixels per image): two waves per 32x32 tile, four residue chains each
-  // (sgemm_sdot_rc.hip; profiles/r03_dw_forms.json: 4-7 % on those layers,
-  // behind this kernel on the 52^2 ones)
-  const int64_t t64 = ((a.M + 63) / 64) * ((a.N + 63) / 64) * a.batch;
-  if (g_sdot_form < 0 && a.K <= 1024 && t64 >= 512 && sdot_rc_applies(a))
-    return launch_sdot_rc(1, a, s);
-  const bool v = k_vec4(a.A, a.lda, a.strideA, a.batch, a.K) &&
-                 k_vec4(a.B, a.ldb, a.strideB, a.batch, a.K);
-  const int64_t b64 = ((a.M + 31) / 32) * ((a.N + 63) / 64) * a.batch;
-  // scalar staging with 32-bit row offsets when each image's A and B fit them
-  const bool o32 = (a.M - 1) * a.lda + a.K <= 0x7fffffffLL && (a.N - 1) * a.ldb + a.K <= 0x7fffffffLL;
-  if (b64 >= 1024)
-    return v ? launch_tn<2, 4>(a, s) : (o32 ? launch_tn<2, 1, 64, true>(a, s) : launch_tn<2, 1>(a, s));
-  // few 32x32 tiles over a long k: 256-deep k-tiles (the 64-row LDS stages
-  // take 2 x 65.8 KB of gfx950's 160 KB)
-  if (a.K >= 16384 && ((a.M + 31) / 32) * ((a.N + 31) / 32) * a.batch < 512)
-    return v ? launch_tn<1, 4, 256>(a, s) : launch_tn<1, 1, 256>(a, s);
-  return v ? launch_tn<1, 4>(a, s) : launch_tn<1, 1>(a, s);
+}
+
+// (which kernel by shape and TNS_OPT_SDOT_FORM: plan_gemm_nt_sdot, gemm_plan.cpp)
+hipError_t launch_sgemm_nt_sdot(const GemmArgs& a, hipStream_t s) {
+  return launch_gemm_plan(plan_gemm_nt_sdot(gemm_shape(a, false, true), g_sdot_form), a, s);
 }
 
 }  // namespace tns

@@ -343,12 +343,6 @@ const ChainsVariant kChains[] = {
 #undef TNS_CHAINS
 constexpr int kChainsCount = sizeof(kChains) / sizeof(kChains[0]);
 
-bool chains_vec4(const float* p, int64_t ld, int64_t stride, int64_t batch, int64_t K) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
-  if (ld % 4 != 0 || K % 4 != 0) return false;
-  return batch <= 1 || stride % 4 == 0;
-}
-
 }  // namespace
 
 int sdot_chains_variant_count() { return kChainsCount; }
@@ -359,8 +353,9 @@ const char* sdot_chains_variant_name(int v) {
 hipError_t launch_sdot_chains(const GemmArgs& a, int variant, hipStream_t s) {
   if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return hipSuccess;
   if (variant < 0 || variant >= kChainsCount) return hipErrorInvalidValue;
-  const bool gl = chains_vec4(a.A, a.lda, a.strideA, a.batch, a.K) &&
-                  chains_vec4(a.B, a.ldb, a.strideB, a.batch, a.K);
+  const GemmShape g = gemm_shape(a, false, true);
+  const bool gl = vec4_ok(g.a16, a.lda, a.strideA, a.batch, a.K) &&
+                  vec4_ok(g.b16, a.ldb, a.strideB, a.batch, a.K);
   return kChains[variant].launch(a, gl, s);
 }
 

@@ -256,18 +256,12 @@ constexpr int kNumForms = sizeof(kForms) / sizeof(kForms[0]);
 int sdot_rc_variant_count() { return kNumForms; }
 const char* sdot_rc_variant_name(int v) { return v >= 0 && v < kNumForms ? kForms[v].name : ""; }
 
-// every image's operands, and the rows a last tile runs past them,
-// byte-addressable in 31 bits (buffer offsets)
-bool sdot_rc_applies(const GemmArgs& a) {
-  const int64_t ea = (a.M + 128) * a.lda + a.K + RC_BK, eb = (a.N + 128) * a.ldb + a.K + RC_BK;
-  return a.M > 0 && a.N > 0 && a.K >= 0 && a.lda >= a.K && a.ldb >= a.K &&
-         ea * 4 < 0x7fffffffLL && eb * 4 < 0x7fffffffLL;
-}
+static_assert(RC_BK == kSdotRcBk, "sdot_rc_applies (gemm_plan.cpp) counts on this k-tile");
 
 hipError_t launch_sdot_rc(int v, const GemmArgs& a, hipStream_t s) {
   if (v < 0 || v >= kNumForms) return hipErrorInvalidValue;
   if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return hipSuccess;
-  if (!sdot_rc_applies(a)) return hipErrorInvalidValue;
+  if (!sdot_rc_applies(gemm_shape(a, false, true))) return hipErrorInvalidValue;
   return kForms[v].fn(a, s);
 }
 

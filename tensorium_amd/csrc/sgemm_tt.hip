@@ -157,12 +157,14 @@ hipError_t launch_r(const GemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// 128x128 tiles (8x8 per thread) when they still give >= 2 blocks per CU,
-// else 64x64 (4x4 per thread)
+// (128x128 or 64x64 tiles: plan_gemm_tt, gemm_plan.cpp)
+hipError_t launch_sgemm_tt_plan(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  if (p.err || p.family != GEMM_TT) return hipErrorInvalidValue;
+  return p.tn == 8 ? launch_r<8>(a, s) : launch_r<4>(a, s);
+}
+
 hipError_t launch_sgemm_tt(const GemmArgs& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return hipSuccess;
-  const int64_t b128 = ((a.M + 127) / 128) * ((a.N + 127) / 128) * a.batch;
-  return b128 >= 512 ? launch_r<8>(a, s) : launch_r<4>(a, s);
+  return launch_gemm_plan(plan_gemm_tt(gemm_shape(a, true, true)), a, s);
 }
 
 }  // namespace tns

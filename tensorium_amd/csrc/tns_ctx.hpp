@@ -301,14 +301,14 @@ inline int do_gemm(tns_ctx* c, bool ta, bool tb, int64_t M, int64_t N, int64_t K
   a.C = C; a.ldc = ldc; a.strideC = sC;
   a.batch = batch; a.epi = epi; a.bias = bias; a.act = act;
   OpTimer t(c, TNS_OP_GEMM);
-  if (!ta && tb && g_opt.nt_sdot && variant < 0 && epi == EPI_NONE)
-    return hip_status(launch_sgemm_nt_sdot(a, c->stream), "sgemm_nt launch");
-  if (ta && tb && g_opt.tt_exact && variant < 0 && epi == EPI_NONE)
-    return hip_status(launch_sgemm_tt(a, c->stream), "sgemm_tt launch");
-  hipError_t e = launch_sgemm_variant(variant, a, ta, tb, c->stream);
-  if (e == hipErrorInvalidValue && variant >= 0)
+  const GemmPlan p = plan_gemm(gemm_shape(a, ta, tb), variant, g_opt, get_sdot_form());
+  // (a forced variant the plan refuses, or whose grid the launch refuses)
+  const hipError_t e = launch_gemm_plan(p, a, c->stream);
+  if ((p.err || e == hipErrorInvalidValue) && variant >= 0)
     return set_error(TNS_ERR_UNSUPPORTED, "gemm variant %d (%s) does not support this problem",
                      variant, sgemm_variant_name(variant));
+  if (p.family == GEMM_TT) return hip_status(e, "sgemm_tt launch");
+  if (p.family >= GEMM_NT_SDOT) return hip_status(e, "sgemm_nt launch");
   return hip_status(e, "sgemm launch");
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/tns.h"
+#include "gemm_plan.hpp"
 
 namespace tns {
 
@@ -81,15 +82,33 @@ struct GemmArgs {
   unsigned* stamps;
 };
 
+// the shape the planners of gemm_plan.hpp see: everything but the pointers,
+// of which only the 16-byte alignment matters
+inline GemmShape gemm_shape(const GemmArgs& a, bool transA, bool transB) {
+  GemmShape s;
+  s.ta = transA; s.tb = transB;
+  s.M = a.M; s.N = a.N; s.K = a.K;
+  s.lda = a.lda; s.ldb = a.ldb; s.ldc = a.ldc;
+  s.strideA = a.strideA; s.strideB = a.strideB; s.strideC = a.strideC;
+  s.batch = a.batch;
+  s.alpha1 = a.alpha == 1.0f;
+  s.beta_mode = a.beta_mode;
+  s.epi = a.epi;
+  s.conv = a.conv != 0;
+  s.a16 = (reinterpret_cast<uintptr_t>(a.A) & 15) == 0;
+  s.b16 = (reinterpret_cast<uintptr_t>(a.B) & 15) == 0;
+  return s;
+}
+// runs what a plan of any family names (hipErrorInvalidValue where p.err)
+hipError_t launch_gemm_plan(const GemmPlan& p, const GemmArgs& a, hipStream_t s);
 hipError_t launch_sgemm(const GemmArgs& a, bool transA, bool transB, hipStream_t s);
 // large aligned NN (M, N multiples of the tile, K of 32; sgemm_nn_big.hip):
-// form v of sgemm_nn_big_count(); pick = -1 when none applies by heuristic
+// form v of kNnBigForms; which problems a form takes and which one the
+// heuristic picks: nn_big_applies / nn_big_pick (gemm_plan.hpp)
 int sgemm_nn_big_count();
 const char* sgemm_nn_big_name(int v);
-int sgemm_nn_big_pick(const GemmArgs& a);
-hipError_t launch_sgemm_nn_big(int v, const GemmArgs& a, hipStream_t s);
+hipError_t launch_sgemm_nn_big(const GemmPlan& p, const GemmArgs& a, hipStream_t s);
 // the 256x256 NN tile on the ping-pong schedule (sgemm_nn_pp.hip; form 5)
-bool sgemm_nn_pp_applies(const GemmArgs& a);
 hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s);
 // the same tile with one wave per SIMD (4 waves of 128 x 128), A and B by
 // LDS-DMA into swizzled row images, interleaved columns (b128 B reads,
@@ -97,9 +116,9 @@ hipError_t launch_sgemm_nn_pp(const GemmArgs& a, hipStream_t s);
 // last two k-tiles run one accumulator row at a time where K >= 128, so the
 // C loads and stores go under MFMAs), 7 (the flat schedule throughout) and 8
 // (rows with pre = false: the regular loop's fragment addresses computed per
-// step instead of held in registers)
-bool sgemm_nn_w4_applies(const GemmArgs& a);
-hipError_t launch_sgemm_nn_w4(const GemmArgs& a, hipStream_t s, bool rows = true, bool pre = true);
+// step instead of held in registers); the plan's rows / pre / alpha1 are the
+// kernel's template arguments
+hipError_t launch_sgemm_nn_w4(const GemmPlan& p, const GemmArgs& a, hipStream_t s);
 // gemm(NoTrans, Trans) in the reference's sdot_avx2 order (sgemm_sdot.hip);
 // plain epilogue only
 hipError_t launch_sgemm_nt_sdot(const GemmArgs& a, hipStream_t s);
@@ -112,15 +131,16 @@ const char* sdot_chains_variant_name(int v);
 // waves' registers (sgemm_sdot_rc.hip)
 int sdot_rc_variant_count();
 const char* sdot_rc_variant_name(int v);
-bool sdot_rc_applies(const GemmArgs& a);
 hipError_t launch_sdot_rc(int v, const GemmArgs& a, hipStream_t s);
-// TNS_OPT_SDOT_FORM: -1 heuristic, 0 the MFMA kernel, 1 + v chains variant v,
-// 64 + v residue-register form v
-constexpr int SDOT_FORM_RC = 64;
+// TNS_OPT_SDOT_FORM as set (SDOT_FORM_RC: gemm_plan.hpp)
 void set_sdot_form(int form);
+int get_sdot_form();
+// the MFMA kernel's launch_tn<p.tn, p.vec, p.bk, p.o32>
+hipError_t launch_sgemm_nt_sdot_tn(const GemmPlan& p, const GemmArgs& a, hipStream_t s);
 // gemm(Trans, Trans) in the reference's scalar s_tt order (sgemm_tt.hip);
 // plain epilogue only
 hipError_t launch_sgemm_tt(const GemmArgs& a, hipStream_t s);
+hipError_t launch_sgemm_tt_plan(const GemmPlan& p, const GemmArgs& a, hipStream_t s);
 // C[e] := (...((C[e] + part[0][e]) + part[1][e]) ...) + part[batch-1][e]
 hipError_t launch_add_in_order(float* C, const float* part, int64_t n, int64_t batch,
                                hipStream_t s);

@@ -443,22 +443,38 @@ def test_4096_cubed_sampled_rows_bit_exact(hip, torch_cuda, ora):
 def test_every_tile_variant_bit_exact(hip, torch_cuda, ora):
     """Each tile shape of the tuning table, forced, on ragged shapes: NN/TN
     bit-exact; variants limited to float4/NN report UNSUPPORTED otherwise."""
+    from _gemm_cases import VARIANT_NAMES, Case, supported
     from tensorium_amd._abi import TnsError
     names = hip.gemmVariants()
+    assert names == VARIANT_NAMES  # the support table is written for this tuning table
+    ran = refused = 0
     for v, name in enumerate(names):
         for (M, N, K) in [(37, 53, 61), (129, 130, 33), (256, 260, 96), (64, 512, 40)]:
             for ta in (0, 1):
                 rng = np.random.default_rng(v * 1000 + M + ta)
                 A, B, C0 = operands(rng, ta, 0, M, N, K)
                 dA, dB, dC = (torch_cuda.from_numpy(x).cuda() for x in (A, B, C0.copy()))
-                try:
+
+                def call():
                     hip.gemmVariant(v, bool(ta), False, M, N, K, 0.5, dA, 0, A.shape[1], 0,
                                     dB, 0, B.shape[1], 0, 2.0, dC, 0, N, 0, 1)
-                except TnsError:
+                    hip.finish()
+                # (the KIND column and the `applies` rules, never the library's word)
+                if not supported(Case("", ta, 0, M, N, K, variant=v, ldc=N)):
+                    with pytest.raises(TnsError):
+                        call()
+                    hip.finish()
+                    assert np.array_equal(dC.cpu().numpy(), C0), (name, M, N, K, ta)
+                    refused += 1
                     continue
-                hip.finish()
+                call()
+                ran += 1
                 ref = run_ref(ora, ta, 0, A, B, C0, 0.5, 2.0)
                 assert np.array_equal(dC.cpu().numpy(), ref), (name, M, N, K, ta)
+    # the 8 launch_full shapes take all 8 problems; launch_trans4 the two with
+    # float4 operands in each transpose; launch_nn4 those two under NN only;
+    # no large-NN form has a multiple of its tile among them
+    assert (ran, refused) == (8 * 8 + 2 * 4 + 13 * 2, 2 * 4 + 13 * 6 + 9 * 8)
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 32), (512, 768, 96), (256, 512, 2080)])
