@@ -63,8 +63,8 @@ def _g(cid, ta, tb, M, N, K, beta=0.0, **kw):
 
 
 def _sub_layer(cid, S, I, O):
-    """A connected (sub-)layer over S rows: forward, dW, dX (darknet.py
-    _fc_forward / _fc_backward, _sub_forward / _sub_backward)."""
+    """A connected (sub-)layer over S rows: forward, dW, dX
+    (darknet/connected.py, forward / backward)."""
     return [_g(f"{cid}/fwd", 0, 1, S, O, I), _g(f"{cid}/dW", 1, 0, O, I, S, 1.0),
             _g(f"{cid}/dX", 0, 0, S, I, O, 1.0)]
 
