@@ -508,6 +508,41 @@ int tns_hip_avgpool_backward(tns_ctx* ctx, int64_t aBatch, int64_t outC, int64_t
                              int64_t w, int64_t stride_x, int64_t stride_y, int64_t padding,
                              int64_t kernelSize);
 
+/* ---- global average pooling (TAvgPoolLayer, navgpoollayer.pas) ---------- */
+/* The layer every darknet classifier ends in ([avgpool]; parseAvgPool,
+ * nparser.pas:294-299): input [aBatch][c][h][w] -> output [aBatch][c].  Here
+ * the data is [planes][n], planes = aBatch*c, n = h*w, planes contiguous.
+ * TNNCuda has no such method — the reference runs this layer on the CPU — so
+ * the two entries carry no tns_hip_ prefix and, like the tns_image_* entries,
+ * join a pending dW of the pipelined conv backward on every call instead of
+ * taking a place in the hazard table.
+ *
+ * tns_pool_global_avg_forward = TAvgPoolLayer.forward (navgpoollayer.pas:
+ * 60-84): output[p] = Sum(plane p) / n.  Sum is vssum_avx2 (ntensors.pas:
+ * 3592-3620): eight accumulators from +0, accumulator j adding elements j,
+ * j+8, j+16, ... of the first 8*(n div 8) in that order; s_j = a_j + a_(j+4)
+ * for j < 4; (s0+s1) + (s2+s3); the n mod 8 tail elements added one at a time
+ * in index order; then one division by float(n).  Every step is one float32
+ * rounding (a plane of -0.0 gives +0.0: the accumulators start at +0).  Eight
+ * lanes own a plane, the two folds run across lanes; a very large plane is a
+ * long sequential chain per lane, the price of the order.
+ *
+ * tns_pool_global_avg_backward = TAvgPoolLayer.backward (navgpoollayer.pas:
+ * 86-108): stateDelta[p*n + i] += delta[p] / float(n) for every i: the
+ * quotient rounded once, then one add per element (16-byte accesses between
+ * the buffer's first and last 16-byte boundary, single elements outside).
+ *
+ * Departures: the reference converts n to the quotient's type at each use;
+ * here float(n) must be exact, so n > 2^24 is refused.  TNS_ERR_ARG, before
+ * anything is launched or written: a negative size; n > 2^24; planes*n beyond
+ * 2^63 bytes (the other pool entries' bound); a null operand where there is
+ * work; output or stateDelta overlapping the other operand.  planes == 0 or
+ * n == 0 does nothing and returns TNS_OK. */
+int tns_pool_global_avg_forward(tns_ctx* ctx, int64_t planes, int64_t n, const float* input,
+                                float* output);
+int tns_pool_global_avg_backward(tns_ctx* ctx, int64_t planes, int64_t n, const float* delta,
+                                 float* stateDelta);
+
 /* ---- dropout and the elementwise loss heads (heads.hip) ----
  * tns_hip_dropout_forward = TNNCuda.forwardDropout, the reference's device
  * kernel (cuda_sgemm.cu:1617-1645), a pure function of (seed, i) — the CPU

@@ -233,6 +233,12 @@ function tns_hip_avgpool_backward(ctx: PTnsCtx; aBatch, outC, outH, outW: int64;
   delta: THipMem; h, w, stride_x, stride_y, padding, kernelSize: int64): longint;
   cdecl; external libtns;
 
+{ the global average pool (TAvgPoolLayer) over [planes][n] }
+function tns_pool_global_avg_forward(ctx: PTnsCtx; planes, n: int64; input,
+  output: THipMem): longint; cdecl; external libtns;
+function tns_pool_global_avg_backward(ctx: PTnsCtx; planes, n: int64; delta,
+  stateDelta: THipMem): longint; cdecl; external libtns;
+
 { dropout (seed in [0, 2^32)) and the elementwise loss heads }
 function tns_hip_dropout_forward(ctx: PTnsCtx; N, seed: int64; probability, scale: single; src,
   rnd, dst: THipMem): longint; cdecl; external libtns;
@@ -402,6 +408,8 @@ type
     procedure backwardMaxPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const indexes, delta: TCUMem; const h: SizeInt = 0; const w: SizeInt = 0; const stride_x: SizeInt = 0; const stride_y: SizeInt = 0; const padding: SizeInt = 0; const kernelSize: SizeInt = 0);
     procedure forwardAvgPool(const aBatch, outC, outH, outW: SizeInt; const input: TCUMem; const c, h, w: SizeInt; const stride_x, stride_y, padding, kernelSize: SizeInt; output: TCUMem);
     procedure backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; output: TCUMem; const delta: TCUMem; const h, w, stride_x, stride_y, padding, kernelSize: SizeInt);
+    procedure forwardGlobalAvgPool(const aBatch, c, h, w: SizeInt; const input: TCUMem; output: TCUMem);
+    procedure backwardGlobalAvgPool(const aBatch, c, h, w: SizeInt; const delta: TCUMem; stateDelta: TCUMem);
     procedure yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);
     procedure yoloDetections(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
     procedure nmsSort(const batch, capacity, classes: SizeInt; const counts, boxes, objectness: TCUMem; probs: TCUMem; const thresh: single);
@@ -687,6 +695,16 @@ procedure TNNHip<T>.backwardAvgPool(const aBatch, outC, outH, outW: SizeInt; out
 begin
   check(tns_hip_avgpool_backward(FCtx, aBatch, outC, outH, outW, THipMem(output), THipMem(delta),
     h, w, stride_x, stride_y, padding, kernelSize))
+end;
+
+procedure TNNHip<T>.forwardGlobalAvgPool(const aBatch, c, h, w: SizeInt; const input: TCUMem; output: TCUMem);
+begin
+  check(tns_pool_global_avg_forward(FCtx, aBatch * c, h * w, THipMem(input), THipMem(output)))
+end;
+
+procedure TNNHip<T>.backwardGlobalAvgPool(const aBatch, c, h, w: SizeInt; const delta: TCUMem; stateDelta: TCUMem);
+begin
+  check(tns_pool_global_avg_backward(FCtx, aBatch * c, h * w, THipMem(delta), THipMem(stateDelta)))
 end;
 
 procedure TNNHip<T>.yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);

@@ -248,6 +248,9 @@ PROTOTYPES.update({
                                           i64, i64, fptr]),
     "tns_hip_avgpool_backward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64,
                                            i64, i64, i64]),
+    # the global average pool over [planes][n]
+    "tns_pool_global_avg_forward": (C.c_int, [vp, i64, i64, fptr, fptr]),
+    "tns_pool_global_avg_backward": (C.c_int, [vp, i64, i64, fptr, fptr]),
     # dropout (the seed an int64 in [0, 2^32)) and the elementwise loss heads
     "tns_hip_dropout_forward": (C.c_int, [vp, i64, i64, f32, f32, fptr, fptr, fptr]),
     "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),

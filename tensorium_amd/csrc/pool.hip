@@ -263,7 +263,120 @@ hipError_t backward(int64_t planes, const PoolGeom& g, float* sd, const int64_t*
   return hipGetLastError();
 }
 
+// ---- global average pool (TAvgPoolLayer, navgpoollayer.pas:60-108) ---------
+// The data is [planes][n], planes contiguous.  Forward: out[p] = Sum(plane p)
+// / float(n), Sum in vssum_avx2's order (ntensors.pas:3592-3620; vssum8 in
+// batchnorm.hip is the one-thread form).  Eight lanes own a plane, lane j
+// being accumulator j: from +0 it adds elements j, j+8, j+16, ... of the
+// first 8*(n div 8); the fold a_j + a_(j+4) and the two pair adds (s0+s1) +
+// (s2+s3) run across the lanes; lane 0 then adds the n mod 8 tail elements in
+// index order and divides once.  A wave64 holds eight planes, a block 32.
+// n is the same for every lane, so every loop trip count is wave-uniform and
+// the cross-lane steps run converged; a lane whose plane is past the end
+// reads the last plane and only its store is masked.
+constexpr int GAP_PLANES = 256 / 8;   // planes per block
+constexpr int GAP_MAX_BLOCKS = 2048;  // 8 resident blocks on each of 256 CUs; beyond: more trips
+
+__global__ __launch_bounds__(256) void global_avgpool_fwd_kernel(int64_t planes, int64_t n,
+                                                                 const float* __restrict__ in,
+                                                                 float* __restrict__ out) {
+  const int l = threadIdx.x & 7;
+  const int64_t nblk = n >> 3;
+  const int64_t nb8 = nblk << 3;
+  const int tail = (int)(n - nb8);
+  const float fn = (float)n;  // exact: n <= 2^24
+  const int64_t groups = (planes + GAP_PLANES - 1) / GAP_PLANES;
+  for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+    const int64_t plane = g * GAP_PLANES + (threadIdx.x >> 3);
+    const bool live = plane < planes;
+    const float* a = in + (live ? plane : planes - 1) * n;
+    float acc = 0.0f;
+    int64_t b = 0;
+    for (; b + 4 <= nblk; b += 4) {  // four loads ahead of the lane's adds
+      const float w0 = a[8 * b + l], w1 = a[8 * b + 8 + l], w2 = a[8 * b + 16 + l],
+                  w3 = a[8 * b + 24 + l];
+      acc = acc + w0;
+      acc = acc + w1;
+      acc = acc + w2;
+      acc = acc + w3;
+    }
+    for (; b < nblk; ++b) acc = acc + a[8 * b + l];
+    const float s = acc + __shfl_down(acc, 4, 8);  // lanes 0..3: a_j + a_(j+4)
+    const float h = s + __shfl_down(s, 1, 8);      // lane 0: s0+s1, lane 2: s2+s3
+    float r = h + __shfl_down(h, 2, 8);            // lane 0: (s0+s1) + (s2+s3)
+    if (tail) {
+      const float tv = l < tail ? a[nb8 + l] : 0.0f;
+      for (int k = 0; k < tail; ++k) r = r + __shfl(tv, k, 8);
+    }
+    if (live && l == 0) out[plane] = r / fn;
+  }
+}
+
+// Backward: state_delta[p*n + i] += delta[p] / float(n), the quotient rounded
+// once (TTensor.Add of a scalar), then one add per element.  The buffer is
+// walked flat: `head` elements up to the first 16-byte boundary and the
+// elements after the last whole group one thread each, float4 groups between;
+// a group may span planes (any n, 1 included), so the plane and its quotient
+// advance inside it.  narrow: total < 2^32, the element's plane by a 32-bit
+// division.
+__global__ __launch_bounds__(256) void global_avgpool_bwd_kernel(int64_t total, int64_t n,
+                                                                 int64_t head, int64_t nvec,
+                                                                 int narrow,
+                                                                 const float* __restrict__ delta,
+                                                                 float* __restrict__ sd) {
+  const float fn = (float)n;
+  const int64_t items = nvec + (total - 4 * nvec);
+  for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items;
+       it += (int64_t)gridDim.x * blockDim.x) {
+    const bool vec = it < nvec;
+    // scalar items: the head elements first, then those after the groups
+    const int64_t k = it - nvec;
+    const int64_t e = vec ? head + 4 * it : (k < head ? k : 4 * nvec + k);
+    int64_t p = narrow ? (int64_t)((uint32_t)e / (uint32_t)n) : e / n;
+    if (!vec) {
+      sd[e] = sd[e] + delta[p] / fn;
+      continue;
+    }
+    int64_t r = e - p * n;
+    float q = delta[p] / fn;
+    float4 t = *reinterpret_cast<float4*>(sd + e);
+    float x[V] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      if (r == n) {
+        r = 0;
+        q = delta[++p] / fn;
+      }
+      x[v] = x[v] + q;
+      ++r;
+    }
+    *reinterpret_cast<float4*>(sd + e) = make_float4(x[0], x[1], x[2], x[3]);
+  }
+}
+
 }  // namespace
+
+hipError_t launch_global_avgpool_forward(int64_t planes, int64_t n, const float* in, float* out,
+                                         hipStream_t s) {
+  const int64_t groups = (planes + GAP_PLANES - 1) / GAP_PLANES;
+  const int blocks = (int)(groups < GAP_MAX_BLOCKS ? groups : GAP_MAX_BLOCKS);
+  hipLaunchKernelGGL(global_avgpool_fwd_kernel, dim3(blocks), dim3(256), 0, s, planes, n, in, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_global_avgpool_backward(int64_t planes, int64_t n, const float* delta,
+                                          float* state_delta, hipStream_t s) {
+  const int64_t total = planes * n;
+  int64_t head = (4 - (int64_t)((reinterpret_cast<uintptr_t>(state_delta) >> 2) & 3)) & 3;
+  if (head > total) head = total;
+  const int64_t nvec = (total - head) / V;
+  const int64_t items = nvec + (total - V * nvec);
+  int64_t blocks = (items + 255) / 256;
+  if (blocks > GAP_MAX_BLOCKS) blocks = GAP_MAX_BLOCKS;
+  hipLaunchKernelGGL(global_avgpool_bwd_kernel, dim3((int)blocks), dim3(256), 0, s, total, n, head,
+                     nvec, total < (int64_t)1 << 32 ? 1 : 0, delta, state_delta);
+  return hipGetLastError();
+}
 
 hipError_t launch_maxpool_forward(int64_t planes, const PoolGeom& g, const float* in, float* out,
                                   int64_t* indexes, hipStream_t s) {

@@ -1277,6 +1277,54 @@ int tns_hip_avgpool_backward(tns_ctx* c, int64_t aBatch, int64_t outC, int64_t o
                     "avgpool backward");
 }
 
+// TAvgPoolLayer.forward / backward (navgpoollayer.pas:60-108), which the
+// reference runs on the CPU: not a TNNCuda method, hence no tns_hip_ prefix;
+// like the tns_image_* entries the two join the side stream on every call
+// instead of taking a place in the hazard table
+namespace {
+// small [planes] is written from (forward) or read into (backward) big
+// [planes][n]; *work: there is something to do
+int global_avg_args(tns_ctx* c, const char* what, int64_t planes, int64_t n, const float* small,
+                    const float* big, bool* work) {
+  if (int r = check_ctx(c)) return r;
+  *work = false;
+  if (planes < 0 || n < 0)
+    return set_error(TNS_ERR_ARG, "%s: negative size (planes %lld, n %lld)", what,
+                     (long long)planes, (long long)n);
+  if (n > (1 << 24))  // float(n) must be exact
+    return set_error(TNS_ERR_ARG, "%s: n %lld beyond 2^24", what, (long long)n);
+  if (planes == 0 || n == 0) return TNS_OK;
+  if (planes > INT64_MAX / 8 / n)
+    return set_error(TNS_ERR_ARG, "%s: buffer beyond 2^63 bytes", what);
+  if (!small || !big) return set_error(TNS_ERR_ARG, "%s: null operand", what);
+  const Span a = span(small, planes), b = span(big, planes * n);
+  if (a.lo < b.hi && b.lo < a.hi)
+    return set_error(TNS_ERR_ARG, "%s: the operands overlap", what);
+  *work = true;
+  return TNS_OK;
+}
+}  // namespace
+
+int tns_pool_global_avg_forward(tns_ctx* c, int64_t planes, int64_t n, const float* input,
+                                float* output) {
+  bool work;
+  if (int r = global_avg_args(c, "global avgpool forward", planes, n, output, input, &work))
+    return r;
+  if (!work) return TNS_OK;
+  return hip_status(launch_global_avgpool_forward(planes, n, input, output, c->stream),
+                    "global avgpool forward");
+}
+
+int tns_pool_global_avg_backward(tns_ctx* c, int64_t planes, int64_t n, const float* delta,
+                                 float* stateDelta) {
+  bool work;
+  if (int r = global_avg_args(c, "global avgpool backward", planes, n, delta, stateDelta, &work))
+    return r;
+  if (!work) return TNS_OK;
+  return hip_status(launch_global_avgpool_backward(planes, n, delta, stateDelta, c->stream),
+                    "global avgpool backward");
+}
+
 // ---- dropout / loss heads (heads.hip) -------------------------------------------
 namespace {
 

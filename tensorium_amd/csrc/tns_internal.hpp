@@ -335,6 +335,13 @@ hipError_t launch_maxpool_backward(int64_t planes, const PoolGeom& g, float* sta
                                    const int64_t* indexes, const float* delta, hipStream_t s);
 hipError_t launch_avgpool_backward(int64_t planes, const PoolGeom& g, float* state_delta,
                                    const float* delta, hipStream_t s);
+// the global average pool (TAvgPoolLayer) over [planes][n]: out[p] =
+// vssum(plane p) / float(n); state_delta[p*n + i] += delta[p] / float(n).
+// The callers have checked 1 <= n <= 2^24 and planes >= 1.
+hipError_t launch_global_avgpool_forward(int64_t planes, int64_t n, const float* in, float* out,
+                                         hipStream_t s);
+hipError_t launch_global_avgpool_backward(int64_t planes, int64_t n, const float* delta,
+                                          float* state_delta, hipStream_t s);
 // heads.hip: dropout (rnd a pure function of seed + i; src == dst allowed)
 // and the elementwise loss heads
 hipError_t launch_dropout_forward(int64_t n, uint32_t seed, float probability, float scale,

@@ -16,7 +16,8 @@ Every public name is importable from this package.
 """
 from .._abi import ACT, TnsError
 from .description import (ACT_SUPPORTED, LSTM_GATES, RNN_SUBS, SEPS, ConvParams, Layer, Network,
-                          Section, cifar10_deep_cfg, fuse_batchnorm, lenet_cifar10_cfg,
+                          Section, cifar10_deep_cfg, darknet19_cfg, darknet53_cfg,
+                          fuse_batchnorm, lenet_cifar10_cfg,
                           lenet_mnist_cfg, load_weights, lstm_cfg, parse_cfg, random_params,
                           rnn_cfg, write_weights, yolov3_cfg, yolov3_tiny_cfg)
 from .drivers import (HipDarknet, HipDarknetTrain, Placement, detection_rows_to_host,

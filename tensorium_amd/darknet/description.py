@@ -12,7 +12,8 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   naddlayer.pas), route (TConcatLayer, nconcatlayer.pas), upsample
   (TUpSampleLayer, nupsamplelayer.pas), yolo (TYoloLayer, nyololayer.pas) and
   maxpool / local_avgpool (TMaxPoolLayer, nMaxPoolLayer.pas:107-109; options
-  as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292), and the
+  as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292), avgpool
+  (TAvgPoolLayer, navgpoollayer.pas; parseAvgPool, nparser.pas:294-299), and the
   classifier kinds connected / dropout / softmax / cost / logistic
   (parseConnected 146-152, parseDropOut 301-331, parseLogistic 714-720,
   parseSoftmax 722-738, parseCost 740-755), and lstm (TLSTMLayer,
@@ -85,8 +86,8 @@ def parse_cfg(text: str) -> list[Section]:
 class Layer:
     index: int
     kind: str            # convolutional | shortcut | route | upsample | yolo |
-                         # maxpool | local_avgpool | connected | dropout |
-                         # softmax | cost | logistic | lstm | rnn
+                         # maxpool | local_avgpool | avgpool | connected |
+                         # dropout | softmax | cost | logistic | lstm | rnn
     c: int               # input channels / height / width
     h: int
     w: int
@@ -208,7 +209,7 @@ ACT_SUPPORTED = tuple(ACT[k] for k in ("LOGISTIC", "RELU", "LINEAR", "TANH", "RE
                                        "HARDTAN"))
 
 _IMAGE_KINDS = ("convolutional", "conv", "shortcut", "route", "concat", "upsample", "yolo",
-                "maxpool", "max", "local_avgpool")
+                "maxpool", "max", "local_avgpool", "avgpool", "avg")
 
 
 class Network:
@@ -299,6 +300,13 @@ class Network:
                 lay = Layer(i, kind, c, h, w, c, (h + padding - size) // sy + 1,
                             (w + padding - size) // sx + 1, size=size, stride=sx, pad=padding,
                             stride_x=sx, stride_y=sy)
+            elif sec.kind in ("avgpool", "avg"):
+                # parseAvgPool (nparser.pas:294-299): the whole plane, no
+                # options; a TBaseImageLayer, so the parser carries on with
+                # c x 1 x 1 (navgpoollayer.pas:27-43)
+                if h * w * c == 0:
+                    raise ValueError("Layer before avgpool layer must output image.")
+                lay = Layer(i, "avgpool", c, h, w, c, 1, 1)
             elif sec.kind in ("connected", "conn"):
                 o = sec.int("output", 1)
                 if o < 1 or c * h * w < 1:
@@ -420,20 +428,30 @@ class Network:
         return [l for l in self.layers if l.kind == "yolo"]
 
 
+def _bn_conv(f, k, s=1, act="leaky", bn=True):
+    return (f"[convolutional]\n{'batch_normalize=1' + chr(10) if bn else ''}"
+            f"filters={f}\nsize={k}\nstride={s}\npad=1\nactivation={act}\n")
+
+
+def _darknet53_backbone() -> list[str]:
+    """Layers 0..74 of YOLOv3, the darknet53 feature extractor: 52
+    convolutions and 23 shortcuts."""
+    out = [_bn_conv(32, 3)]
+    for n, c in ((1, 64), (2, 128), (8, 256), (8, 512), (4, 1024)):
+        out.append(_bn_conv(c, 3, 2))
+        for _ in range(n):
+            out += [_bn_conv(c // 2, 1), _bn_conv(c, 3),
+                    "[shortcut]\nfrom=-3\nactivation=linear\n"]
+    return out
+
+
 def yolov3_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
     """The darknet YOLOv3 network (the public yolov3.cfg structure; the
     reference loads that file from outside its tree, MSCOCOYolo.pas:28-34)."""
     out = [f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={size}\nheight={size}\nchannels=3\n"]
 
     def conv(f, k, s=1, act="leaky", bn=True):
-        out.append(f"[convolutional]\n{'batch_normalize=1' + chr(10) if bn else ''}"
-                   f"filters={f}\nsize={k}\nstride={s}\npad=1\nactivation={act}\n")
-
-    def res(n, c):
-        for _ in range(n):
-            conv(c // 2, 1)
-            conv(c, 3)
-            out.append("[shortcut]\nfrom=-3\nactivation=linear\n")
+        out.append(_bn_conv(f, k, s, act, bn))
 
     anchors = "10,13, 16,30, 33,23, 30,61, 62,45, 59,119, 116,90, 156,198, 373,326"
 
@@ -442,12 +460,7 @@ def yolov3_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
                    "jitter=.3\nignore_thresh = .7\ntruth_thresh = 1\nrandom=1\n")
 
     det = 3 * (classes + 5)
-    conv(32, 3)
-    conv(64, 3, 2); res(1, 64)
-    conv(128, 3, 2); res(2, 128)
-    conv(256, 3, 2); res(8, 256)
-    conv(512, 3, 2); res(8, 512)
-    conv(1024, 3, 2); res(4, 1024)
+    out += _darknet53_backbone()
     for _ in range(2):
         conv(512, 1); conv(1024, 3)
     conv(512, 1); conv(1024, 3); conv(det, 1, act="linear", bn=False)
@@ -503,6 +516,38 @@ def yolov3_tiny_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
     out.append("[route]\nlayers = -1, 8\n")
     conv(256, 3); conv(det, 1, act="linear", bn=False)
     yolo("0,1,2")
+    return "\n".join(out)
+
+
+def darknet19_cfg(size: int = 256, batch: int = 1, classes: int = 1000) -> str:
+    """The darknet19 ImageNet classifier (the public darknet19.cfg structure;
+    the file is not in the reference's tree, so this is the common structure,
+    not a file that can be compared against): 3x3 batch-normalised leaky
+    convolutions of 32 and 64 filters, each followed by a 2x2/2 max pool; the
+    groups 128-64-128, 256-128-256, 512-256-512-256-512 (each followed by a
+    pool) and 1024-512-1024-512-1024, their middle convolutions 1x1; a 1x1
+    linear convolution to ``classes`` without batch norm; [avgpool]; [softmax].
+    26 layers, 19 of them convolutional."""
+    out = [f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={size}\nheight={size}\nchannels=3\n"]
+    pool = "[maxpool]\nsize=2\nstride=2\n"
+    out += [_bn_conv(32, 3), pool, _bn_conv(64, 3), pool]
+    for c, n in ((128, 3), (256, 3), (512, 5), (1024, 5)):
+        out += [_bn_conv(c if k % 2 == 0 else c // 2, 3 if k % 2 == 0 else 1) for k in range(n)]
+        if c != 1024:
+            out.append(pool)
+    out += [_bn_conv(classes, 1, act="linear", bn=False), "[avgpool]\n", "[softmax]\ngroups=1\n"]
+    return "\n".join(out)
+
+
+def darknet53_cfg(size: int = 256, batch: int = 1, classes: int = 1000) -> str:
+    """The darknet53 ImageNet classifier (the public darknet53.cfg structure;
+    the file is not in the reference's tree, so this is the common structure,
+    not a file that can be compared against): YOLOv3's layers 0..74, then
+    [avgpool], a linear [connected] to ``classes`` and [softmax].  78 layers."""
+    out = [f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={size}\nheight={size}\nchannels=3\n"]
+    out += _darknet53_backbone()
+    out += ["[avgpool]\n", f"[connected]\noutput={classes}\nactivation=linear\n",
+            "[softmax]\ngroups=1\n"]
     return "\n".join(out)
 
 

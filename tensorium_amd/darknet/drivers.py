@@ -212,6 +212,8 @@ class _Driver(_RnnLayers, _LstmLayers):
         elif l.kind == "local_avgpool":
             hip.forwardAvgPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
                                l.stride_y, l.pad, l.size, out)
+        elif l.kind == "avgpool":
+            hip.forwardGlobalAvgPool(B, l.c, l.h, l.w, prev, out)
         elif l.kind == "softmax":
             g = l.in_size // l.groups
             hip.softmaxBatch(g, prev, 0, B, l.in_size, l.groups, g, 1, l.temperature, out, 0)
@@ -392,6 +394,10 @@ class HipDarknetTrain(_Driver):
       689-706; CPU loops 501-542): ``backwardMaxPool`` with the indexes its
       forward stored, or ``backwardAvgPool``, accumulating into state.delta;
       nothing when the pool is layer 0 (no state.delta);
+    * avgpool (TAvgPoolLayer.forward / backward, navgpoollayer.pas:60-108,
+      which the reference runs on the CPU): ``forwardGlobalAvgPool``;
+      ``backwardGlobalAvgPool`` accumulating delta / (h*w) into state.delta,
+      nothing when it is layer 0;
     * connected (TConnectedLayer.forwardGPU / backwardGPU, nconnectedlayer.pas:
       612-871): ``connected.forward`` / ``connected.backward`` over one step
       of ``batch`` rows;
@@ -600,6 +606,29 @@ class HipDarknetTrain(_Driver):
             if st is not None:
                 fc.update(self.hip, st, self.net.batch, learning_rate, momentum, decay)
 
+    def export_params(self) -> list[ConvParams]:
+        """The trained parameters read back from the device state, one
+        ConvParams per block in ``Network.param_layers()`` order
+        (convolutional and connected layers, an lstm layer's eight and an rnn
+        layer's three sub-layers): weights and biases, and scales and the
+        rolling mean and variance when batch-normalised — what saveWeights
+        stores (nparser.pas:1227-1273).  ``write_weights(path, net,
+        train.export_params())`` writes the file ``load_weights`` and
+        ``HipDarknet`` run as the trained network."""
+        self.hip.finish()
+        ps = []
+        for l in self.net.param_layers():
+            if l.gate:
+                owner = self.lstm if self.net.layers[l.index].kind == "lstm" else self.rnn
+                st = owner[l.index]["sub"][l.gate]
+            else:
+                st = self.conv[l.index] if l.kind == "convolutional" else self.fc[l.index]
+            host = lambda k: st[k].detach().cpu().numpy().astype(np.float32, copy=True)  # noqa: E731
+            w = host("w").reshape(l.filters, -1)
+            bn = [host(k) for k in ("scales", "rm", "rv")] if l.bn else []
+            ps.append(ConvParams(host("b"), w, *bn))
+        return ps
+
     def set_yolo_deltas(self, deltas):
         """The yolo layers' deltas (what their training forward's loss would
         leave), in layer order."""
@@ -650,6 +679,8 @@ class HipDarknetTrain(_Driver):
             elif l.kind == "local_avgpool" and sd is not None:
                 hip.backwardAvgPool(B, l.out_c, l.out_h, l.out_w, sd, d, l.h, l.w, l.stride_x,
                                     l.stride_y, l.pad, l.size)
+            elif l.kind == "avgpool" and sd is not None:
+                hip.backwardGlobalAvgPool(B, l.c, l.h, l.w, d, sd)
             elif l.kind == "connected":
                 fc.backward(hip, self.fc[i], B, 0, inp.reshape(-1), 0, sd, 0)
             elif l.kind == "lstm":

@@ -275,6 +275,18 @@ class TNNHip:
                                                 _ptr(delta), h, w, stride_x, stride_y, padding,
                                                 kernelSize))
 
+    def forwardGlobalAvgPool(self, aBatch, c, h, w, input, output):
+        """TAvgPoolLayer.forward (navgpoollayer.pas:60-84): output[aBatch][c]
+        = Sum(plane) / (h*w), Sum in vssum_avx2's order."""
+        check(self.lib.tns_pool_global_avg_forward(self.ctx, aBatch * c, h * w, _ptr(input),
+                                                   _ptr(output)))
+
+    def backwardGlobalAvgPool(self, aBatch, c, h, w, delta, stateDelta):
+        """TAvgPoolLayer.backward (navgpoollayer.pas:86-108): stateDelta
+        [aBatch][c][h][w] += delta[aBatch][c] / (h*w)."""
+        check(self.lib.tns_pool_global_avg_backward(self.ctx, aBatch * c, h * w, _ptr(delta),
+                                                    _ptr(stateDelta)))
+
     def addvv(self, N, src1, src1Offset, inca, src2, src2Offset, incb, dst, dstOffset, incc):
         check(self.lib.tns_hip_addvv(self.ctx, N, _ptr(src1), src1Offset, inca, _ptr(src2),
                                      src2Offset, incb, _ptr(dst), dstOffset, incc))
