@@ -357,8 +357,8 @@ int tns_hip_yolo_loss(tns_ctx* ctx, int64_t batch, int64_t anchors, int64_t clas
  * capacity afterwards is how the caller learns of it (the reference's count
  * pass and fill pass in one).  So the layers of a network append into one
  * buffer when called in network order on counts zeroed once.  Nothing outside
- * the taken rows is written.  Not built: new_coords, the embedding output,
- * TRegionLayer.  A letterbox whose scaled extent truncates to 0 divides by
+ * the taken rows is written.  Not built: new_coords, the embedding output
+ * (TRegionLayer: tns_region_detections).  A letterbox whose scaled extent truncates to 0 divides by
  * zero as the reference does; the result is then IEEE's, not an exception.
  * TNS_ERR_ARG, before anything is launched or written: a negative size; netW,
  * netH, imW or imH below 1 or above 2^24; a null operand where there is work
@@ -542,6 +542,73 @@ int tns_pool_global_avg_forward(tns_ctx* ctx, int64_t planes, int64_t n, const f
                                 float* output);
 int tns_pool_global_avg_backward(tns_ctx* ctx, int64_t planes, int64_t n, const float* delta,
                                  float* stateDelta);
+
+/* ---- the region layer, YOLOv2's head (region.hip) ----
+ * TRegionLayer (nregionlayer.pas), which the reference runs on the CPU only:
+ * no TNNCuda method, hence no tns_hip_ prefix; like the tns_pool_global_avg_*
+ * and tns_image_* entries the three join a pending dW of the pipelined conv
+ * backward on every call instead of taking a place in the hazard table.
+ * Built: coords = 4, no tree, no map, no focal loss.  size = classes + 5.
+ *
+ * tns_region_forward = TRegionLayer.forward's inference part (lines 297-325
+ * with flatten 97-116 and softmax 129-152): input [batch][num*size][hw] (the
+ * convolution's output) becomes output [batch][hw][num][size]; entry 4 of
+ * every (cell, anchor) goes through 1/(1+exp(-x)) (double from the exp on,
+ * rounded once), and with softmax != 0 entries 5.. through softmax(classes,
+ * temp 1): the max scan from entry 5, e = exp((x-largest)/1) stored as a
+ * single, the ascending single sum, the divide.  Entries 0..3 are copied.
+ * TNS_ERR_ARG, before anything is launched or written: a negative size; a
+ * buffer beyond 2^31 elements or batch above 65535; num*size above 8192 (one
+ * cell's channels must fit the tile); a null operand where there is work;
+ * input and output overlapping.  An empty tensor is a successful no-op.
+ *
+ * tns_region_loss = the training part (lines 328-480) on that output, bit
+ * for bit the CPU loop's delta and cost.  truth [batch][maxBoxes][6] on the
+ * device, rows x, y, w, h, class, track_id; in both loops a row whose class
+ * is >= classes is skipped before the x == 0 test that ends the list.
+ * biases (2*num floats) is a HOST array, copied before the call returns;
+ * seen is state.seen^ (below 12800 the prior-box deltaBox at scale 0.01
+ * runs).  Writes delta [batch][num*size][hw] (the un-flattened order, every
+ * element: delta.fill(0) is part of the call) and cost[0] =
+ * sqr(delta.sumSquares()), the ascending single chain over that order, then
+ * squared.  output is only read.  The avg_* / recall statistics are not
+ * computed.  Departures: a truth whose cell trunc(x*w), trunc(y*h) lies
+ * outside the grid is skipped in the truth pass (the reference writes out of
+ * bounds), and so is a truth whose class is NaN; a truth that overlaps no
+ * anchor (every shifted iou 0) is written to anchor 0 of its own cell (the
+ * reference's best_index stays 0: element 0 of the whole batch).
+ * TNS_ERR_ARG, before anything is launched or written: a negative size or
+ * seen; a null operand; maxBoxes outside [1, 2048]; num above 32; num*size
+ * above 8192; batch above 65535; a buffer beyond 2^31 elements.
+ *
+ * tns_region_detections = getDetections + getBoxes + correct_yolo_boxes
+ * (lines 534-690) for all images, appended to the row buffers of
+ * tns_hip_yolo_detections under the same count / capacity contract (rows
+ * behind counts[b]; counts[b] grows by the rows taken, fitting or not;
+ * nothing outside the taken rows is written), so tns_hip_nms_sort serves
+ * them.  Per (cell, anchor), cell outer, anchor inner: scale = entry 4, 0
+ * when classfix == -1 and it is < 0.5; prob[j] = scale * class_j where that
+ * is > thresh, else 0; objectness = 1; bbox = getBox (the logistic of
+ * entries 0, 1; exp(entry) * bias / w in double) after correct_yolo_boxes.
+ * Departures: the reference emits all w*h*num rows; here a row is taken only
+ * when at least one prob[j] is non-zero (a dropped row can neither be drawn
+ * nor suppress anything in doNMSSort).  The reference hands the layer's own
+ * w, h to correct_yolo_boxes as the image's extents (getDetections' width /
+ * height arguments are never read); here imW, imH are the image's, as
+ * TYoloLayer.getDetections has it.  TNS_ERR_ARG as tns_hip_yolo_detections
+ * (without mask and total), and num*size above 8192. */
+int tns_region_forward(tns_ctx* ctx, int64_t batch, int64_t num, int64_t classes, int64_t hw,
+                       int32_t softmax, const float* input, float* output);
+int tns_region_loss(tns_ctx* ctx, int64_t batch, int64_t num, int64_t classes, int64_t h,
+                    int64_t w, const float* biases, int64_t maxBoxes, int64_t seen,
+                    int32_t rescore, int32_t biasMatch, int32_t classfix, float thresh,
+                    float coordScale, float objectScale, float noobjectScale, float classScale,
+                    const float* output, const float* truth, float* delta, float* cost);
+int tns_region_detections(tns_ctx* ctx, int64_t batch, int64_t num, int64_t classes, int64_t h,
+                          int64_t w, const float* biases, int32_t classfix, int64_t netW,
+                          int64_t netH, int64_t imW, int64_t imH, float thresh, int32_t relative,
+                          int32_t letter, const float* output, int64_t capacity, int64_t* counts,
+                          float* boxes, float* objectness, float* probs);
 
 /* ---- dropout and the elementwise loss heads (heads.hip) ----
  * tns_hip_dropout_forward = TNNCuda.forwardDropout, the reference's device

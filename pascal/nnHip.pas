@@ -239,6 +239,20 @@ function tns_pool_global_avg_forward(ctx: PTnsCtx; planes, n: int64; input,
 function tns_pool_global_avg_backward(ctx: PTnsCtx; planes, n: int64; delta,
   stateDelta: THipMem): longint; cdecl; external libtns;
 
+{ TRegionLayer (nregionlayer.pas): forward (flatten + logistic + softmax), the training
+  loss (delta un-flattened, cost = sqr(sumSquares)) and getDetections into the row buffers
+  of tns_hip_yolo_detections; biases is the layer's host array (2*num) }
+function tns_region_forward(ctx: PTnsCtx; batch, num, classes, hw: int64; softmax: longint;
+  input, output: THipMem): longint; cdecl; external libtns;
+function tns_region_loss(ctx: PTnsCtx; batch, num, classes, h, w: int64; biases: PSingle;
+  maxBoxes, seen: int64; rescore, biasMatch, classfix: longint; thresh, coordScale,
+  objectScale, noobjectScale, classScale: single; output, truth, delta,
+  cost: THipMem): longint; cdecl; external libtns;
+function tns_region_detections(ctx: PTnsCtx; batch, num, classes, h, w: int64; biases: PSingle;
+  classfix: longint; netW, netH, imW, imH: int64; thresh: single; relative, letter: longint;
+  output: THipMem; capacity: int64; counts: PInt64; boxes, objectness,
+  probs: THipMem): longint; cdecl; external libtns;
+
 { dropout (seed in [0, 2^32)) and the elementwise loss heads }
 function tns_hip_dropout_forward(ctx: PTnsCtx; N, seed: int64; probability, scale: single; src,
   rnd, dst: THipMem): longint; cdecl; external libtns;
@@ -413,6 +427,9 @@ type
     procedure yoloLoss(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const maxBoxes, netW, netH: SizeInt; const ignoreThresh, truthThresh, iouThresh, iouNormalizer, objNormalizer: single; output: TCUMem; const truth: TCUMem; delta, cost, stats, counters: TCUMem);
     procedure yoloDetections(const batch, anchors, classes, h, w, total: SizeInt; const mask: PSizeInt; const biases: PSingle; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
     procedure nmsSort(const batch, capacity, classes: SizeInt; const counts, boxes, objectness: TCUMem; probs: TCUMem; const thresh: single);
+    procedure regionForward(const batch, num, classes, hw: SizeInt; const softmax: boolean; const input: TCUMem; output: TCUMem);
+    procedure regionLoss(const batch, num, classes, h, w: SizeInt; const biases: PSingle; const maxBoxes, seen: SizeInt; const rescore, biasMatch: boolean; const classfix: longint; const thresh, coordScale, objectScale, noobjectScale, classScale: single; const output, truth: TCUMem; delta, cost: TCUMem);
+    procedure regionDetections(const batch, num, classes, h, w: SizeInt; const biases: PSingle; const classfix: longint; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
     procedure imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64 = nil);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
@@ -735,6 +752,34 @@ begin
     their place }
   check(tns_hip_nms_sort(FCtx, batch, capacity, classes, PInt64(counts), THipMem(boxes),
     THipMem(objectness), THipMem(probs), thresh))
+end;
+
+procedure TNNHip<T>.regionForward(const batch, num, classes, hw: SizeInt; const softmax: boolean; const input: TCUMem; output: TCUMem);
+begin
+  { TRegionLayer.forward's inference part: state.input [batch][num*(classes+5)][hw]
+    to output [batch][hw][num][classes+5], logistic on entry 4, class softmax }
+  check(tns_region_forward(FCtx, batch, num, classes, hw, ord(softmax), THipMem(input),
+    THipMem(output)))
+end;
+
+procedure TNNHip<T>.regionLoss(const batch, num, classes, h, w: SizeInt; const biases: PSingle; const maxBoxes, seen: SizeInt; const rescore, biasMatch: boolean; const classfix: longint; const thresh, coordScale, objectScale, noobjectScale, classScale: single; const output, truth: TCUMem; delta, cost: TCUMem);
+begin
+  { the training part on what regionForward left: biases = layer.biases.data
+    (host), seen = state.seen^; delta comes back un-flattened, cost[0] =
+    sqr(delta.sumSquares()) }
+  check(tns_region_loss(FCtx, batch, num, classes, h, w, biases, maxBoxes, seen, ord(rescore),
+    ord(biasMatch), classfix, thresh, coordScale, objectScale, noobjectScale, classScale,
+    THipMem(output), THipMem(truth), THipMem(delta), THipMem(cost)))
+end;
+
+procedure TNNHip<T>.regionDetections(const batch, num, classes, h, w: SizeInt; const biases: PSingle; const classfix: longint; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
+begin
+  { the [region] layer's getDetections for every image, appended like
+    yoloDetections' rows: call the detection layers in network order on counts
+    zeroed once }
+  check(tns_region_detections(FCtx, batch, num, classes, h, w, biases, classfix, netW, netH, imW,
+    imH, thresh, ord(relative), ord(letter), THipMem(output), capacity, PInt64(counts),
+    THipMem(boxes), THipMem(objectness), THipMem(probs)))
 end;
 
 procedure TNNHip<T>.imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64);

@@ -251,6 +251,12 @@ PROTOTYPES.update({
     # the global average pool over [planes][n]
     "tns_pool_global_avg_forward": (C.c_int, [vp, i64, i64, fptr, fptr]),
     "tns_pool_global_avg_backward": (C.c_int, [vp, i64, i64, fptr, fptr]),
+    # the region layer: biases a host array; counts a device int64[batch]
+    "tns_region_forward": (C.c_int, [vp, i64, i64, i64, i64, i32, fptr, fptr]),
+    "tns_region_loss": (C.c_int, [vp, i64, i64, i64, i64, i64, C.POINTER(f32), i64, i64, i32, i32,
+                                  i32, f32, f32, f32, f32, f32, fptr, fptr, fptr, fptr]),
+    "tns_region_detections": (C.c_int, [vp, i64, i64, i64, i64, i64, C.POINTER(f32), i32, i64, i64,
+                                        i64, i64, f32, i32, i32, fptr, i64, vp, fptr, fptr, fptr]),
     # dropout (the seed an int64 in [0, 2^32)) and the elementwise loss heads
     "tns_hip_dropout_forward": (C.c_int, [vp, i64, i64, f32, f32, fptr, fptr, fptr]),
     "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),

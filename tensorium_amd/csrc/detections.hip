@@ -10,7 +10,8 @@
 //   nms      TDetections.doNMSSort (ntypes.pas:1554-1565, 1612-1649) on such a
 //            buffer, in place on prob.
 //
-// Collect is an ordered compaction in three launches: the taken candidates of
+// Collect is an ordered compaction in three launches (the rank and the scan:
+// det_scan.hpp, shared with region.hip): the taken candidates of
 // every 256-candidate chunk are counted, one block an image scans the chunk
 // counts behind the image's counter (and adds the total to it), and every
 // chunk then writes its rows from its own offset.  A row's place is the
@@ -30,13 +31,13 @@
 // a real (double) and its expression stays double until it is assigned to a
 // single; integer / integer is a real; everything else is single with every
 // operation rounded.  [s] single, [d] double, [i] integer.
+#include "det_scan.hpp"
 #include "tns_internal.hpp"
 #include "yolo_box.hpp"
 
 namespace tns {
 namespace {
 
-constexpr int kDetChunk = 256;  // candidates per block of the collect kernels
 constexpr int kNmsThreads = 256;
 constexpr int kNmsLds = 2048;  // candidates of one (image, class) the sorted form holds
 
@@ -54,24 +55,6 @@ __device__ __forceinline__ bool det_taken(const DetParams& p, const float* __res
   return out[det_entry(p, b, c % p.n, c / p.n, 4)] > p.thresh;
 }
 
-// the taken candidates of this block's chunk before this thread's, and the
-// chunk's total
-__device__ __forceinline__ int det_chunk_rank(bool taken, int* total) {
-  __shared__ int s_wave[kDetChunk / 64];
-  const unsigned long long m = __ballot(taken);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kDetChunk / 64; ++k) {
-    if (k < wave) before += s_wave[k];
-    all += s_wave[k];
-  }
-  *total = all;
-  return before + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 // grid (chunks, batch)
 __global__ void __launch_bounds__(kDetChunk)
 det_count_kernel(DetParams p, const float* __restrict__ out, int* __restrict__ chunk_counts) {
@@ -79,36 +62,6 @@ det_count_kernel(DetParams p, const float* __restrict__ out, int* __restrict__ c
   int total;
   det_chunk_rank(det_taken(p, out, b, blockIdx.x * kDetChunk + threadIdx.x), &total);
   if (threadIdx.x == 0) chunk_counts[(int64_t)b * gridDim.x + blockIdx.x] = total;
-}
-
-// grid (batch): chunk_offsets[b][c] = counts[b] + the chunks before c; then
-// counts[b] += the image's taken candidates, fitting or not
-__global__ void __launch_bounds__(256)
-det_scan_kernel(int chunks, const int* __restrict__ chunk_counts,
-                long long* __restrict__ chunk_offsets, long long* __restrict__ counts) {
-  __shared__ int s[256];
-  __shared__ long long s_carry;
-  const int b = blockIdx.x;
-  if (threadIdx.x == 0) s_carry = counts[b];
-  __syncthreads();
-  for (int c0 = 0; c0 < chunks; c0 += 256) {
-    const int c = c0 + threadIdx.x;
-    const int mine = c < chunks ? chunk_counts[(int64_t)b * chunks + c] : 0;
-    s[threadIdx.x] = mine;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {  // inclusive scan
-      const int add = (int)threadIdx.x >= d ? s[threadIdx.x - d] : 0;
-      __syncthreads();
-      s[threadIdx.x] += add;
-      __syncthreads();
-    }
-    const long long carry = s_carry;
-    if (c < chunks) chunk_offsets[(int64_t)b * chunks + c] = carry + s[threadIdx.x] - mine;
-    __syncthreads();
-    if (threadIdx.x == 255) s_carry = carry + s[255];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[b] = s_carry;
 }
 
 // getBox (nyololayer.pas:105-122), not newCoords, then correctBoxes (452-498)
@@ -121,32 +74,7 @@ __device__ __forceinline__ Box det_box(const DetParams& p, const float o[4], int
   // exp(out) [d] * bias [d] / netWidth [d], rounded on the assignment
   b.w = (float)(exp((double)o[2]) * (double)p.biases[2 * an] / (double)p.netW);
   b.h = (float)(exp((double)o[3]) * (double)p.biases[2 * an + 1] / (double)p.netH);
-  // correctBoxes: w, h are the image's extents from here on
-  long long new_w = p.netW, new_h = p.netH;  // [i]
-  if (p.letter) {
-    // (netw / w) [d] < (neth / h) [d]: integer / integer is a real
-    if ((double)p.netW / (double)p.imW < (double)p.netH / (double)p.imH)
-      new_h = ((long long)p.imH * p.netW) / p.imW;  // [i] (h * netw) div w
-    else
-      new_w = ((long long)p.imW * p.netH) / p.imH;  // [i] (w * neth) div h
-  }
-  const float deltaw = (float)(p.netW - new_w);  // [i] difference, assigned to a single
-  const float deltah = (float)(p.netH - new_h);
-  const float ratiow = (float)((double)new_w / (double)p.netW);  // [d] quotient, rounded once
-  const float ratioh = (float)((double)new_h / (double)p.netH);
-  // (b.x - deltaw / 2.0 / netw) / ratiow: deltaw / 2.0 [s], / netw [s], the
-  // difference [s], / ratiow [s]
-  b.x = (b.x - deltaw / 2.0f / (float)p.netW) / ratiow;
-  b.y = (b.y - deltah / 2.0f / (float)p.netH) / ratioh;
-  b.w = b.w * (1.0f / ratiow);  // (1 / ratiow) [s], the product [s]
-  b.h = b.h * (1.0f / ratioh);
-  if (!p.relative) {
-    b.x = b.x * (float)p.imW;  // [s] single * integer
-    b.w = b.w * (float)p.imW;
-    b.y = b.y * (float)p.imH;
-    b.h = b.h * (float)p.imH;
-  }
-  return b;
+  return correct_box(b, p.netW, p.netH, p.imW, p.imH, p.relative, p.letter);
 }
 
 // grid (chunks, batch)
@@ -331,7 +259,7 @@ nms_sort_kernel(int capacity, int classes, const long long* __restrict__ counts,
 
 int64_t detections_scratch_floats(const DetParams& p) {
   const int64_t chunks = ((int64_t)p.h * p.w * p.n + kDetChunk - 1) / kDetChunk;
-  return 3 * chunks * p.batch;  // offsets (int64), then counts (int)
+  return det_scan_scratch_floats(chunks, p.batch);
 }
 
 hipError_t launch_yolo_detections(const DetParams& p, const float* out, int64_t* counts,

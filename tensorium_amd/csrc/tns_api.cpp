@@ -1325,6 +1325,113 @@ int tns_pool_global_avg_backward(tns_ctx* c, int64_t planes, int64_t n, const fl
                     "global avgpool backward");
 }
 
+// ---- the region layer (region.hip) -----------------------------------------------
+// TRegionLayer runs on the CPU in the reference: not a TNNCuda method, hence
+// no tns_hip_ prefix; the three entries join the side stream on every call
+// (check_ctx) instead of taking a place in the hazard table
+namespace {
+// the sizes every region entry shares; *n: the tensor's elements
+int region_sizes(const char* what, int64_t batch, int64_t num, int64_t classes, int64_t hw,
+                 int64_t* n) {
+  if (batch < 0 || num < 0 || classes < 0 || hw < 0)
+    return set_error(TNS_ERR_ARG, "%s: negative size", what);
+  const int64_t lim = 0x3fffffff;
+  if (classes > lim || num > lim || num * (classes + 5) > 8192)
+    return set_error(TNS_ERR_ARG, "%s: num*(classes+5) = %lld channels above 8192", what,
+                     (long long)(num > lim || classes > lim ? -1 : num * (classes + 5)));
+  if (batch > 65535 || hw > lim ||
+      batch * num * (classes + 5) > 0x7fff0000 / std::max<int64_t>(hw, 1))
+    return set_error(TNS_ERR_ARG, "%s: batch beyond 65535, or a buffer beyond 2^31 elements",
+                     what);
+  *n = batch * num * (classes + 5) * hw;
+  return TNS_OK;
+}
+}  // namespace
+
+int tns_region_forward(tns_ctx* c, int64_t batch, int64_t num, int64_t classes, int64_t hw,
+                       int32_t softmax, const float* input, float* output) {
+  if (int r = check_ctx(c)) return r;
+  int64_t n = 0;
+  if (int r = region_sizes("region forward", batch, num, classes, hw, &n)) return r;
+  if (n == 0) return TNS_OK;
+  if (!input || !output) return set_error(TNS_ERR_ARG, "region forward: null operand");
+  const Span a = span(input, n), b = span(output, n);
+  if (a.lo < b.hi && b.lo < a.hi)
+    return set_error(TNS_ERR_ARG, "region forward: input and output overlap");
+  return hip_status(launch_region_forward((int)batch, (int)num, (int)classes, (int)hw,
+                                          softmax != 0, input, output, c->stream),
+                    "region forward");
+}
+
+int tns_region_loss(tns_ctx* c, int64_t batch, int64_t num, int64_t classes, int64_t h, int64_t w,
+                    const float* biases, int64_t maxBoxes, int64_t seen, int32_t rescore,
+                    int32_t biasMatch, int32_t classfix, float thresh, float coordScale,
+                    float objectScale, float noobjectScale, float classScale, const float* output,
+                    const float* truth, float* delta, float* cost) {
+  if (int r = check_ctx(c)) return r;
+  if (h < 0 || w < 0 || seen < 0 || h > 0x3fffffff || w > 0x3fffffff)
+    return set_error(TNS_ERR_ARG, "region loss: negative size or seen");
+  int64_t n = 0;
+  if (int r = region_sizes("region loss", batch, num, classes, h * w, &n)) return r;
+  if (maxBoxes < 1 || maxBoxes > kYoloMaxBoxes)
+    return set_error(TNS_ERR_ARG, "region loss: maxBoxes %lld outside [1, %d]",
+                     (long long)maxBoxes, kYoloMaxBoxes);
+  if (num > kYoloMaxAnchors)
+    return set_error(TNS_ERR_ARG, "region loss: more than %d anchors", kYoloMaxAnchors);
+  if (!output || !truth || !delta || !cost || (num > 0 && !biases))
+    return set_error(TNS_ERR_ARG, "region loss: null operand");
+  if (n == 0)  // nothing to sum
+    return hip_status(launch_fill(1, cost, 0.0f, 1, c->stream), "region loss");
+  RegionParams p{};
+  for (int64_t i = 0; i < 2 * num; ++i) p.biases[i] = biases[i];
+  p.batch = (int)batch, p.n = (int)num, p.classes = (int)classes, p.h = (int)h, p.w = (int)w;
+  p.maxBoxes = (int)maxBoxes, p.rescore = rescore != 0, p.biasMatch = biasMatch != 0;
+  p.classfix = classfix, p.prior = seen < 12800;
+  p.thresh = thresh, p.coordScale = coordScale, p.objectScale = objectScale;
+  p.noobjectScale = noobjectScale, p.classScale = classScale;
+  float* scratch = nullptr;
+  if (int r = ensure_scratch(c, SLOT_YOLO, region_loss_scratch_floats(n), &scratch)) return r;
+  return hip_status(launch_region_loss(p, output, truth, delta, cost, scratch, c->stream),
+                    "region loss");
+}
+
+int tns_region_detections(tns_ctx* c, int64_t batch, int64_t num, int64_t classes, int64_t h,
+                          int64_t w, const float* biases, int32_t classfix, int64_t netW,
+                          int64_t netH, int64_t imW, int64_t imH, float thresh, int32_t relative,
+                          int32_t letter, const float* output, int64_t capacity, int64_t* counts,
+                          float* boxes, float* objectness, float* probs) {
+  if (int r = check_ctx(c)) return r;
+  if (h < 0 || w < 0 || h > 0x3fffffff || w > 0x3fffffff || netW < 1 || netH < 1 || imW < 1 ||
+      imH < 1 || netW > (1 << 24) || netH > (1 << 24) || imW > (1 << 24) || imH > (1 << 24))
+    return set_error(TNS_ERR_ARG, "region detections: negative size, or a network / image "
+                                  "extent outside [1, 2^24]");
+  int64_t n = 0;
+  if (int r = region_sizes("region detections", batch, num, classes, h * w, &n)) return r;
+  if (capacity < 1 || capacity > kDetMaxCapacity)
+    return set_error(TNS_ERR_ARG, "region detections: capacity %lld outside [1, %d]",
+                     (long long)capacity, kDetMaxCapacity);
+  if (num > kYoloMaxAnchors)
+    return set_error(TNS_ERR_ARG, "region detections: more than %d anchors", kYoloMaxAnchors);
+  if (batch * capacity > 0x7fff0000 / std::max<int64_t>(classes, 4))
+    return set_error(TNS_ERR_ARG, "region detections: a row buffer beyond 2^31 elements");
+  const bool work = batch > 0 && num > 0 && h * w > 0;
+  if (!work) return TNS_OK;
+  if (!output || !counts || !boxes || !objectness || (classes > 0 && !probs) || !biases)
+    return set_error(TNS_ERR_ARG, "region detections: null operand");
+  RegionParams p{};
+  for (int64_t i = 0; i < 2 * num; ++i) p.biases[i] = biases[i];
+  p.batch = (int)batch, p.n = (int)num, p.classes = (int)classes, p.h = (int)h, p.w = (int)w;
+  p.classfix = classfix, p.netW = (int)netW, p.netH = (int)netH, p.imW = (int)imW;
+  p.imH = (int)imH, p.relative = relative != 0, p.letter = letter != 0;
+  p.capacity = (int)capacity, p.thresh = thresh;
+  float* scratch = nullptr;
+  if (int r = ensure_scratch(c, SLOT_YOLO, region_detections_scratch_floats(p), &scratch))
+    return r;
+  return hip_status(launch_region_detections(p, output, counts, boxes, objectness, probs, scratch,
+                                             c->stream),
+                    "region detections");
+}
+
 // ---- dropout / loss heads (heads.hip) -------------------------------------------
 namespace {
 

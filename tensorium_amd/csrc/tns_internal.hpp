@@ -412,6 +412,30 @@ hipError_t launch_yolo_detections(const DetParams& p, const float* out, int64_t*
 hipError_t launch_nms_sort(int batch, int capacity, int classes, const int64_t* counts,
                            const float* boxes, const float* objectness, float* probs,
                            float thresh, hipStream_t s);
+// region.hip: TRegionLayer (nregionlayer.pas).  Forward: in [batch][n*(classes
+// +5)][hw] to out [batch][hw][n][classes+5], entry 4 through the logistic and,
+// with softmax, entries 5.. through the per-cell softmax.  Loss: the training
+// part of TRegionLayer.forward on that output; delta comes back un-flattened,
+// [batch][n*(classes+5)][hw].  Detections: getDetections + correct_yolo_boxes
+// into the rows behind counts[b].  biases (2*n) by value.
+constexpr int kRegionLds = 64 * 1024;  // the forward tile's LDS budget, bytes
+struct RegionParams {
+  int batch, n, classes, h, w, maxBoxes;
+  int rescore, biasMatch, classfix, prior;  // prior: seen < 12800
+  int netW, netH, imW, imH, relative, letter, capacity;  // detections
+  float thresh, coordScale, objectScale, noobjectScale, classScale;
+  float biases[2 * kYoloMaxAnchors];
+};
+int region_tile_cells(int64_t channels);  // T; 0: one cell's channels exceed kRegionLds
+hipError_t launch_region_forward(int batch, int n, int classes, int hw, int softmax,
+                                 const float* in, float* out, hipStream_t s);
+int64_t region_loss_scratch_floats(int64_t n);
+hipError_t launch_region_loss(const RegionParams& p, const float* out, const float* truth,
+                              float* delta, float* cost, float* scratch, hipStream_t s);
+int64_t region_detections_scratch_floats(const RegionParams& p);
+hipError_t launch_region_detections(const RegionParams& p, const float* out, int64_t* counts,
+                                    float* boxes, float* objectness, float* probs,
+                                    float* scratch, hipStream_t s);
 // image.hip: TImageData.resize / letterBox of `count` images into dst
 // [count][channels][netH][netW].  One image's geometry, worked out on the
 // host: its first element from src (bytes or floats), row stride, extent, the

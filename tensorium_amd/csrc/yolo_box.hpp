@@ -1,6 +1,7 @@
 // yolo_box.hpp — TBox's overlap / box_iou (ntypes.pas:1059-1108) in the
-// single-precision form the reference computes, shared by yolo_loss.hip and
-// detections.hip.  Compiled with -ffp-contract=off; [s] marks a single.
+// single-precision form the reference computes, and the box correction the
+// detections end with, shared by yolo_loss.hip, detections.hip and
+// region.hip.  Compiled with -ffp-contract=off; [s] marks a single.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,38 @@ __device__ __forceinline__ float box_iou(const Box& a, const Box& b) {
   const float U = a.w * a.h + b.w * b.h - I;  // [s] two products, their sum, minus I
   if (I == 0.0f || U == 0.0f) return 0.0f;
   return I / U;  // [s]
+}
+
+// TYoloLayer.correctBoxes (nyololayer.pas:452-498) and correct_yolo_boxes
+// (nregionlayer.pas:607-653), the same expressions, on one box; imW, imH are
+// the image's extents.  [d] double, [i] integer.
+__device__ __forceinline__ Box correct_box(Box b, int netW, int netH, int imW, int imH,
+                                           int relative, int letter) {
+  long long new_w = netW, new_h = netH;  // [i]
+  if (letter) {
+    // (netw / w) [d] < (neth / h) [d]: integer / integer is a real
+    if ((double)netW / (double)imW < (double)netH / (double)imH)
+      new_h = ((long long)imH * netW) / imW;  // [i] (h * netw) div w
+    else
+      new_w = ((long long)imW * netH) / imH;  // [i] (w * neth) div h
+  }
+  const float deltaw = (float)(netW - new_w);  // [i] difference, assigned to a single
+  const float deltah = (float)(netH - new_h);
+  const float ratiow = (float)((double)new_w / (double)netW);  // [d] quotient, rounded once
+  const float ratioh = (float)((double)new_h / (double)netH);
+  // (b.x - deltaw / 2.0 / netw) / ratiow: deltaw / 2.0 [s], / netw [s], the
+  // difference [s], / ratiow [s]
+  b.x = (b.x - deltaw / 2.0f / (float)netW) / ratiow;
+  b.y = (b.y - deltah / 2.0f / (float)netH) / ratioh;
+  b.w = b.w * (1.0f / ratiow);  // (1 / ratiow) [s], the product [s]
+  b.h = b.h * (1.0f / ratioh);
+  if (!relative) {
+    b.x = b.x * (float)imW;  // [s] single * integer
+    b.w = b.w * (float)imW;
+    b.y = b.y * (float)imH;
+    b.h = b.h * (float)imH;
+  }
+  return b;
 }
 
 }  // namespace

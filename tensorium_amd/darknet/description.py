@@ -10,7 +10,8 @@ and the layer plan of a forward pass — the part of TDarknetParser / TNNet
   (``pad=1`` => padding = size div 2, nparser.pas:186-189; out = (in + 2p - k)
   div stride + 1, nConvolutionLayer.pas:92-100), shortcut (TAddLayer,
   naddlayer.pas), route (TConcatLayer, nconcatlayer.pas), upsample
-  (TUpSampleLayer, nupsamplelayer.pas), yolo (TYoloLayer, nyololayer.pas) and
+  (TUpSampleLayer, nupsamplelayer.pas), yolo (TYoloLayer, nyololayer.pas),
+  region (TRegionLayer, nregionlayer.pas; parseRegion, nparser.pas:646-712) and
   maxpool / local_avgpool (TMaxPoolLayer, nMaxPoolLayer.pas:107-109; options
   as parseMaxPool / parseLocalAvgPool read them, nparser.pas:248-292), avgpool
   (TAvgPoolLayer, navgpoollayer.pas; parseAvgPool, nparser.pas:294-299), and the
@@ -85,7 +86,7 @@ def parse_cfg(text: str) -> list[Section]:
 @dataclass
 class Layer:
     index: int
-    kind: str            # convolutional | shortcut | route | upsample | yolo |
+    kind: str            # convolutional | shortcut | route | upsample | yolo | region |
                          # maxpool | local_avgpool | avgpool | connected |
                          # dropout | softmax | cost | logistic | lstm | rnn
     c: int               # input channels / height / width
@@ -128,6 +129,17 @@ class Layer:
     obj_normalizer: float = 1.0
     delta_normalizer: float = 1.0
     unbuilt: tuple = ()        # the keys set that the device loss does not build
+    # region (parseRegion, nparser.pas:646-712): anchors = total = num=, classes,
+    # biases (2*num) and max_boxes as above; the scales and thresh float32 values
+    softmax: bool = False
+    rescore: bool = False
+    bias_match: bool = False
+    classfix: int = 0
+    thresh: float = 0.5
+    coord_scale: float = 1.0
+    object_scale: float = 1.0
+    noobject_scale: float = 1.0
+    class_scale: float = 1.0
 
     def __post_init__(self):
         self.stride_x = self.stride_x or self.stride
@@ -193,6 +205,37 @@ def _yolo_loss_fields(sec: Section, mask: list) -> dict:
                 delta_normalizer=_f32(sec, "delta_normalizer", 1.0), unbuilt=tuple(unbuilt))
 
 
+def _region_layer(sec: Section, i: int, c: int, h: int, w: int) -> Layer:
+    """parseRegion (nparser.pas:646-712) and TRegionLayer.Create
+    (nregionlayer.pas:44-71).  Refused: coords other than 4 (getBoxes
+    hard-codes classes+5), tree=, map= and focal_loss=1, which are not built.
+    An absent tree= / map= means no tree and no map (the reference's parser
+    builds a non-empty file name even then)."""
+    coords, classes, num = sec.int("coords", 4), sec.int("classes", 20), sec.int("num", 1)
+    if coords != 4:
+        raise ValueError(f"[region] layer {i}: coords={coords} is not built (4 only)")
+    for key in ("tree", "map"):
+        if str(sec.get(key, "")).strip():
+            raise ValueError(f"[region] layer {i}: {key}= is not built")
+    if _flag(sec, "focal_loss"):
+        raise ValueError(f"[region] layer {i}: focal_loss=1 is not built")
+    if c != num * (classes + coords + 1):
+        raise ValueError("Error: l.outputs == params.inputs, filters= in the [convolutional]-layer "
+                         "doesn't correspond to classes= or num= in [region]-layer")
+    vals = [v for v in str(sec.get("anchors", "")).split(",") if v.strip()]
+    biases = [np.float32(0.5)] * (2 * num)  # TRegionLayer.Create: biases.Fill(0.5)
+    for k in range(min(len(vals), 2 * num)):
+        biases[k] = np.float32(float(vals[k].strip()))
+    return Layer(i, "region", c, h, w, c, h, w, anchors=num, classes=classes, total=num,
+                 biases=tuple(float(v) for v in biases), max_boxes=sec.int("max", 200),
+                 softmax=_flag(sec, "softmax"), rescore=_flag(sec, "rescore"),
+                 bias_match=_flag(sec, "bias_match"), classfix=sec.int("classfix", 0),
+                 thresh=_f32(sec, "thresh", 0.5), coord_scale=_f32(sec, "coord_scale", 1),
+                 object_scale=_f32(sec, "object_scale", 1),
+                 noobject_scale=_f32(sec, "noobject_scale", 1),
+                 class_scale=_f32(sec, "class_scale", 1))
+
+
 # [net] keys that switch on what the device yolo loss does not build: the
 # adversarial branch and the bad-label rejection block (nyololayer.pas:589-613,
 # 896-990; nparser.pas:975-977)
@@ -209,7 +252,7 @@ ACT_SUPPORTED = tuple(ACT[k] for k in ("LOGISTIC", "RELU", "LINEAR", "TANH", "RE
                                        "HARDTAN"))
 
 _IMAGE_KINDS = ("convolutional", "conv", "shortcut", "route", "concat", "upsample", "yolo",
-                "maxpool", "max", "local_avgpool", "avgpool", "avg")
+                "region", "maxpool", "max", "local_avgpool", "avgpool", "avg")
 
 
 class Network:
@@ -279,6 +322,8 @@ class Network:
                             **_yolo_loss_fields(sec, mask))
                 if c != len(mask) * (classes + 5):
                     raise ValueError(f"yolo layer {i}: {c} channels for {len(mask)} anchors")
+            elif sec.kind == "region":
+                lay = _region_layer(sec, i, c, h, w)
             elif sec.kind in ("maxpool", "max", "local_avgpool"):
                 # parseMaxPool / parseLocalAvgPool (nparser.pas:248-292), shapes
                 # TMaxPoolLayer.Create (nMaxPoolLayer.pas:79-82, 107-109)
@@ -427,6 +472,10 @@ class Network:
     def yolos(self) -> list[Layer]:
         return [l for l in self.layers if l.kind == "yolo"]
 
+    def detectors(self) -> list[Layer]:
+        """The layers TNNet.Detections reads, in network order."""
+        return [l for l in self.layers if l.kind in ("yolo", "region")]
+
 
 def _bn_conv(f, k, s=1, act="leaky", bn=True):
     return (f"[convolutional]\n{'batch_normalize=1' + chr(10) if bn else ''}"
@@ -516,6 +565,24 @@ def yolov3_tiny_cfg(size: int = 416, batch: int = 1, classes: int = 80) -> str:
     out.append("[route]\nlayers = -1, 8\n")
     conv(256, 3); conv(det, 1, act="linear", bn=False)
     yolo("0,1,2")
+    return "\n".join(out)
+
+
+def tiny_yolo_voc_cfg(size: int = 416, batch: int = 1, classes: int = 20) -> str:
+    """The darknet tiny-yolo-voc network (the public tiny-yolo-voc.cfg
+    structure, YOLOv2's small VOC detector): six conv + maxpool stages, the
+    last pool 2x2 with stride 1, two 3x3 convolutions of 1024 filters, the
+    1x1 head of 5*(classes+5) filters and a [region] layer with the cfg's
+    five anchors and scales."""
+    out = [f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={size}\nheight={size}\nchannels=3\n"]
+    for f in (16, 32, 64, 128, 256, 512):
+        out += [_bn_conv(f, 3), f"[maxpool]\nsize=2\nstride={1 if f == 512 else 2}\n"]
+    out += [_bn_conv(1024, 3), _bn_conv(1024, 3),
+            _bn_conv(5 * (classes + 5), 1, act="linear", bn=False),
+            "[region]\nanchors = 1.08,1.19,  3.42,4.41,  6.63,11.38,  9.42,5.11,  16.62,10.52\n"
+            f"bias_match=1\nclasses={classes}\ncoords=4\nnum=5\nsoftmax=1\njitter=.2\nrescore=1\n"
+            "object_scale=5\nnoobject_scale=1\nclass_scale=1\ncoord_scale=1\nabsolute=1\n"
+            "thresh = .6\nrandom=1\n"]
     return "\n".join(out)
 
 

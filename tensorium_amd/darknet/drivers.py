@@ -209,6 +209,8 @@ class _Driver(_RnnLayers, _LstmLayers):
             hip.upSample(B, l.c, l.h, l.w, prev, l.stride, 1, 1.0, out)
         elif l.kind == "yolo":
             hip.yoloForward(B, l.anchors, l.classes, l.h * l.w, prev, out)
+        elif l.kind == "region":
+            hip.regionForward(B, l.anchors, l.classes, l.h * l.w, l.softmax, prev, out)
         elif l.kind == "local_avgpool":
             hip.forwardAvgPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
                                l.stride_y, l.pad, l.size, out)
@@ -232,6 +234,9 @@ class HipDarknet(_Driver):
     forwardBias, then ActivateArray).  A dropout layer's output is its
     input buffer and nothing runs (ndropoutlayer.pas:156-161); softmax is
     softmaxBatch, logistic copy + ActivateArray, cost nothing (no truth).
+    A region layer is ``regionForward`` (TRegionLayer.forward's inference
+    part, which the reference runs on the CPU): its output is cell-major,
+    [batch][h*w][num][classes+5], and ``detections`` reads it as such.
     An lstm layer (``_LstmLayers``) carries c and h from one forward to the
     next until ``reset_state()``; its batch-normalized sub-layers normalize
     by the rolling statistics.  An rnn layer (``_RnnLayers``) likewise carries
@@ -278,8 +283,9 @@ class HipDarknet(_Driver):
                    capacity=None):
         """TNNet.Detections (nnet.pas:584-677) for every image of the batch,
         then TDetections.doNMSSort (ntypes.pas:1612-1649) when ``nms`` is a
-        threshold, on the device; call it after ``forward``.  The [yolo]
-        layers are collected in network order into one row buffer
+        threshold, on the device; call it after ``forward``.  The [yolo] and
+        [region] layers (``regionDetections``: objectness 1, a row only where
+        a class probability passes) are collected in network order into one row buffer
         (TNNHip.yoloDetections appends through a per-image device counter),
         so the rows stand in the reference's order: layer, then cell, then
         anchor.  Returns, per image, ``(boxes [rows, 4], objectness [rows],
@@ -290,13 +296,13 @@ class HipDarknet(_Driver):
         anchors*h*w over the yolo layers, cannot overflow, a smaller one
         raises TnsError when an image has more taken candidates."""
         hip, torch, B = self.hip, self.torch, self.net.batch
-        yolos = self.net.yolos()
+        yolos = self.net.detectors()
         if not yolos:
-            raise ValueError("detections: the network has no [yolo] layer")
+            raise ValueError("detections: the network has no [yolo] or [region] layer")
         # the reference sizes every row's prob by the first layer's classes
         # (nnet.pas:625) and lets a later layer write its own count into it
         if len({l.classes for l in yolos}) > 1:
-            raise ValueError("detections: the [yolo] layers disagree on classes: "
+            raise ValueError("detections: the detection layers disagree on classes: "
                              f"{[l.classes for l in yolos]}")
         bad = [f"layer {l.index} {k}" for l in yolos for k in l.unbuilt
                if k in ("new_coords", "embedding_layer")]
@@ -316,6 +322,11 @@ class HipDarknet(_Driver):
         counts, boxes, obj, probs = self._det
         hip.fill(2 * B, counts.data_ptr(), 0, 0.0, 1)  # int64 zeros, on the backend's stream
         for l in yolos:
+            if l.kind == "region":
+                hip.regionDetections(B, l.anchors, classes, l.h, l.w, l.biases, l.classfix,
+                                     self.net.w, self.net.h, im_w, im_h, thresh, relative, letter,
+                                     self.out[l.index], cap, counts, boxes, obj, probs)
+                continue
             hip.yoloDetections(B, l.anchors, classes, l.h, l.w, l.total, l.mask, l.biases,
                                self.net.w, self.net.h, im_w, im_h, thresh, relative, letter,
                                self.out[l.index], cap, counts, boxes, obj, probs)
@@ -390,6 +401,11 @@ class HipDarknetTrain(_Driver):
       layer's cost from the truth boxes (``yoloLoss``, TYoloLayer.forward
       under state.isTraining, nyololayer.pas:835-1003); without it
       ``set_yolo_deltas`` supplies the delta;
+    * region (TRegionLayer.forward / backward, nregionlayer.pas:288-496, which
+      the reference runs on the CPU): ``regionForward``; with truth
+      ``regionLoss`` fills its delta and cost, ``seen`` being this object's
+      image count (``self.seen``, advanced by the batch at the end of
+      ``backward``, nnet.pas:367); backward ``addvv`` of its delta into state.delta;
     * maxpool / local_avgpool (TMaxPoolLayer.backwardGPU, nMaxPoolLayer.pas:
       689-706; CPU loops 501-542): ``backwardMaxPool`` with the indexes its
       forward stored, or ``backwardAvgPool``, accumulating into state.delta;
@@ -454,6 +470,10 @@ class HipDarknetTrain(_Driver):
         self.costs = {l.index: z(1) for l in net.layers if l.kind in self.LOSS_KINDS}
         # the device yolo loss: cost[1] and the per-image {count, tot_iou} of
         # every yolo layer, and the network's {totalBBox, rewrittenBBox}
+        self.seen = 0  # net.seen: the images trained on (state.seen^ of a region layer)
+        for l in net.layers:
+            if l.kind == "region":
+                self.costs[l.index] = z(1)
         self.yolo_stats = {}
         if self.yolo_loss:
             for l in yolos:
@@ -485,9 +505,9 @@ class HipDarknetTrain(_Driver):
         truth [batch, max_boxes*6] that ``forward`` takes under
         ``yolo_loss``."""
         net, torch = self.net, self.torch
-        yolos = net.yolos()
+        yolos = net.detectors()
         if not yolos:
-            raise ValueError("load_batch: the network has no [yolo] layer")
+            raise ValueError("load_batch: the network has no [yolo] or [region] layer")
         if len(images) != net.batch or len(boxes) != net.batch:
             raise ValueError(f"{len(images)} images and {len(boxes)} box lists for a batch of "
                              f"{net.batch}")
@@ -561,10 +581,18 @@ class HipDarknetTrain(_Driver):
         return self.out
 
     def _loss(self, l, out, truth):
-        """What a yolo, softmax or logistic layer's training forward adds
+        """What a yolo, region, softmax or logistic layer's training forward adds
         when there is truth: its delta and its cost."""
         hip, B, n = self.hip, self.net.batch, self.net.batch * l.in_size
-        if l.kind == "yolo" and self.yolo_loss:
+        if l.kind == "region":
+            if truth.numel() != B * l.max_boxes * 6:
+                raise ValueError(f"truth has {truth.numel()} floats, batch {B} x max "
+                                 f"{l.max_boxes} x 6 expected")
+            hip.regionLoss(B, l.anchors, l.classes, l.h, l.w, l.biases, l.max_boxes, self.seen,
+                           l.rescore, l.bias_match, l.classfix, l.thresh, l.coord_scale,
+                           l.object_scale, l.noobject_scale, l.class_scale, out, truth,
+                           self.delta[l.index], self.costs[l.index])
+        elif l.kind == "yolo" and self.yolo_loss:
             if truth.numel() != B * l.max_boxes * 6:
                 raise ValueError(f"truth has {truth.numel()} floats, batch {B} x max "
                                  f"{l.max_boxes} x 6 expected")
@@ -689,9 +717,10 @@ class HipDarknetTrain(_Driver):
                 self._rnn_backward(l, inp, sd)
             elif l.kind == "dropout" and sd is not None:
                 hip.backwardDropout(sd.numel(), sd, l.probability, l.scale, self.rnd[i], sd)
-            elif l.kind in ("softmax", "logistic") and sd is not None:
+            elif l.kind in ("softmax", "logistic", "region") and sd is not None:
                 hip.addvv(d.numel(), d, 0, 1, sd, 0, 1, sd, 0, 1)
             elif l.kind == "cost" and sd is not None:
                 hip.axpy(d.numel(), l.scale, d, 0, 1, sd, 0, 1)
             if on_backward is not None:
                 on_backward(l)
+        self.seen += B  # Inc(seen, batch)

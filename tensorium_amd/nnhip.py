@@ -358,6 +358,46 @@ class TNNHip:
             float(thresh), int(bool(relative)), int(bool(letter)), _ptr(output), capacity,
             _iptr(counts), _ptr(boxes), _ptr(objectness), _ptr(probs)))
 
+    def regionForward(self, batch, num, classes, hw, softmax, inp, out):
+        """TRegionLayer.forward's inference part (tns_region_forward): inp
+        [batch][num*(classes+5)][hw] to out [batch][hw][num][classes+5], the
+        logistic on entry 4 and, with ``softmax``, the class softmax."""
+        check(self.lib.tns_region_forward(self.ctx, batch, num, classes, hw, int(bool(softmax)),
+                                          _ptr(inp), _ptr(out)))
+
+    @staticmethod
+    def _region_biases(what, num, biases):
+        biases = [float(v) for v in biases]
+        if len(biases) != 2 * num:
+            raise TnsError(f"{what}: {len(biases)} biases for num={num}")
+        return (C.c_float * max(len(biases), 1))(*biases)
+
+    def regionLoss(self, batch, num, classes, h, w, biases, maxBoxes, seen, rescore, biasMatch,
+                   classfix, thresh, coordScale, objectScale, noobjectScale, classScale, output,
+                   truth, delta, cost):
+        """TRegionLayer.forward's training part (tns_region_loss).  biases: a
+        host sequence (2*num); output (what regionForward left), truth
+        [batch][maxBoxes][6], delta [batch][num*(classes+5)][h*w], cost:
+        device float tensors; seen: the images trained on so far."""
+        bs = self._region_biases("regionLoss", num, biases)
+        check(self.lib.tns_region_loss(
+            self.ctx, batch, num, classes, h, w, bs, maxBoxes, int(seen), int(bool(rescore)),
+            int(bool(biasMatch)), int(classfix), float(thresh), float(coordScale),
+            float(objectScale), float(noobjectScale), float(classScale), _ptr(output),
+            _ptr(truth), _ptr(delta), _ptr(cost)))
+
+    def regionDetections(self, batch, num, classes, h, w, biases, classfix, netW, netH, imW, imH,
+                         thresh, relative, letter, output, capacity, counts, boxes, objectness,
+                         probs):
+        """TRegionLayer.getDetections + correct_yolo_boxes for all images
+        (tns_region_detections), appended to yoloDetections' row buffers
+        under the same counts / capacity contract."""
+        bs = self._region_biases("regionDetections", num, biases)
+        check(self.lib.tns_region_detections(
+            self.ctx, batch, num, classes, h, w, bs, int(classfix), netW, netH, imW, imH,
+            float(thresh), int(bool(relative)), int(bool(letter)), _ptr(output), capacity,
+            _iptr(counts), _ptr(boxes), _ptr(objectness), _ptr(probs)))
+
     def nmsSort(self, batch, capacity, classes, counts, boxes, objectness, probs, thresh):
         """TDetections.doNMSSort on the rows yoloDetections left, in place on
         probs (tns_hip_nms_sort); rows keep their place."""
