@@ -610,6 +610,47 @@ int tns_region_detections(tns_ctx* ctx, int64_t batch, int64_t num, int64_t clas
                           int32_t letter, const float* output, int64_t capacity, int64_t* counts,
                           float* boxes, float* objectness, float* probs);
 
+/* ---- bf16 convolution forward, opt-in reduced-precision inference (conv_bf16.hip) ----
+ * The layer's product on the bf16 MFMA: weights and input pixels rounded to
+ * bf16 (nearest even), their products (exact in fp32) accumulated in fp32,
+ * then the fp32 bias, the activation and an fp32 store.  Not bit-exact against
+ * tns_hip_conv_forward and not meant to be: the result lies within
+ * (K + 2) * 2^-23 * (conv(|w~|, |x~|) + |b|) of the exact convolution of the
+ * rounded operands (K = C*kSize*kSize), in an accumulation order that is
+ * unspecified and differs between tile shapes.  Deterministic: no atomics, the
+ * same call gives the same bits.  Nothing else in the library takes these
+ * entries' path by itself; like tns_region_* they are no TNNCuda methods and
+ * join a pending dW of the pipelined conv backward on every call.
+ *
+ * tns_conv_bf16_packed_bytes: *bytes = the size of the packed weight buffer
+ * of a filters x K matrix (filters padded to the tile height, K to the MFMA
+ * step).  TNS_ERR_ARG: filters or K not positive or beyond 2^28, bytes null.
+ *
+ * tns_conv_bf16_pack: one launch; weights [filters][K] (row-major, k in the
+ * (c, ky, kx) order) rounded to bf16, nearest even, Inf and NaN kept, into
+ * packed (16-byte aligned device memory of tns_conv_bf16_packed_bytes bytes)
+ * in the forward kernel's fragment order, zeros in the padding.  The layout is
+ * private to the library.  TNS_ERR_ARG: sizes as above, a null or misaligned
+ * operand, weights and packed overlapping.
+ *
+ * tns_conv_bf16_forward: tensor shapes and meaning of tns_hip_conv_forward at
+ * dilation 1 with biases (batch norm folded by the caller): input
+ * [batch][C][H][W] and out [batch][filters][oh][ow] fp32, packed what
+ * tns_conv_bf16_pack wrote for filters x C*kSize*kSize.  TNS_ERR_UNSUPPORTED:
+ * an activation the library does not implement.  TNS_ERR_ARG, nothing
+ * launched or written: a null operand, a non-positive size (negative
+ * padding), an empty output, input and out overlapping, H + padding or W +
+ * padding or kSize at or beyond 16384, an image or K beyond the 32-bit gather.
+ * TNS_OPT_CONV_BF16_TILE (default -1: by shape; v >= 0: tile v, 0 = 128 x 128,
+ * 1 = 64 x 64) forces the tile shape. */
+int tns_conv_bf16_packed_bytes(tns_ctx* ctx, int64_t filters, int64_t K, int64_t* bytes);
+int tns_conv_bf16_pack(tns_ctx* ctx, int64_t filters, int64_t K, const float* weights,
+                       void* packed);
+int tns_conv_bf16_forward(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int64_t W,
+                          const float* input, const void* packed, const float* biases,
+                          int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
+                          int32_t activation, float* out);
+
 /* ---- dropout and the elementwise loss heads (heads.hip) ----
  * tns_hip_dropout_forward = TNNCuda.forwardDropout, the reference's device
  * kernel (cuda_sgemm.cu:1617-1645), a pure function of (seed, i) — the CPU
@@ -1082,7 +1123,8 @@ enum { TNS_OPT_STRICT_BETA0 = 0, TNS_OPT_CONV_VARIANT = 1, TNS_OPT_CONV_PAD = 2,
        TNS_OPT_NT_SDOT = 3, TNS_OPT_SRSS_QUIRK = 4, TNS_OPT_TT_EXACT = 5,
        TNS_OPT_SDOT_FORM = 6, TNS_OPT_DX_FUSED = 7, TNS_OPT_DX_TILE = 8,
        TNS_OPT_DW_TILE = 9, TNS_OPT_BWD_OVERLAP = 10, TNS_OPT_DX_CONV = 11,
-       TNS_OPT_DW_RES = 12, TNS_OPT_DERIVE_SUMS = 13, TNS_OPT_SCRATCH_CAP = 14 };
+       TNS_OPT_DW_RES = 12, TNS_OPT_DERIVE_SUMS = 13, TNS_OPT_SCRATCH_CAP = 14,
+       TNS_OPT_CONV_BF16_TILE = 15 };
 int tns_set_option(int32_t opt, int64_t value);
 
 #ifdef __cplusplus

@@ -66,6 +66,7 @@ const
   TNS_OPT_DW_RES = 12;
   TNS_OPT_DERIVE_SUMS = 13;
   TNS_OPT_SCRATCH_CAP = 14;
+  TNS_OPT_CONV_BF16_TILE = 15;
 
 type
   PTnsCtx = pointer;
@@ -253,6 +254,16 @@ function tns_region_detections(ctx: PTnsCtx; batch, num, classes, h, w: int64; b
   output: THipMem; capacity: int64; counts: PInt64; boxes, objectness,
   probs: THipMem): longint; cdecl; external libtns;
 
+{ the opt-in bf16 convolution forward (conv_bf16.hip): weights packed once as bf16 in the
+  kernel's own layout, fp32 input / biases / output, fp32 accumulation; not bit-exact }
+function tns_conv_bf16_packed_bytes(ctx: PTnsCtx; filters, K: int64; bytes: PInt64): longint;
+  cdecl; external libtns;
+function tns_conv_bf16_pack(ctx: PTnsCtx; filters, K: int64; weights: THipMem;
+  packedWeights: pointer): longint; cdecl; external libtns;
+function tns_conv_bf16_forward(ctx: PTnsCtx; batch, C, H, W: int64; input: THipMem;
+  packedWeights: pointer; biases: THipMem; filters, kSize, stride, padding: int64;
+  activation: longint; output: THipMem): longint; cdecl; external libtns;
+
 { dropout (seed in [0, 2^32)) and the elementwise loss heads }
 function tns_hip_dropout_forward(ctx: PTnsCtx; N, seed: int64; probability, scale: single; src,
   rnd, dst: THipMem): longint; cdecl; external libtns;
@@ -430,6 +441,9 @@ type
     procedure regionForward(const batch, num, classes, hw: SizeInt; const softmax: boolean; const input: TCUMem; output: TCUMem);
     procedure regionLoss(const batch, num, classes, h, w: SizeInt; const biases: PSingle; const maxBoxes, seen: SizeInt; const rescore, biasMatch: boolean; const classfix: longint; const thresh, coordScale, objectScale, noobjectScale, classScale: single; const output, truth: TCUMem; delta, cost: TCUMem);
     procedure regionDetections(const batch, num, classes, h, w: SizeInt; const biases: PSingle; const classfix: longint; const netW, netH, imW, imH: SizeInt; const thresh: single; const relative, letter: boolean; const output: TCUMem; const capacity: SizeInt; counts, boxes, objectness, probs: TCUMem);
+    function convBf16PackedBytes(const filters, K: SizeInt): SizeInt;
+    procedure convBf16Pack(const filters, K: SizeInt; const weights: TCUMem; packedWeights: TCUMem);
+    procedure convForwardBf16(const batch, C, H, W: SizeInt; const input, packedWeights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
     procedure imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64 = nil);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
@@ -780,6 +794,32 @@ begin
   check(tns_region_detections(FCtx, batch, num, classes, h, w, biases, classfix, netW, netH, imW,
     imH, thresh, ord(relative), ord(letter), THipMem(output), capacity, PInt64(counts),
     THipMem(boxes), THipMem(objectness), THipMem(probs)))
+end;
+
+function TNNHip<T>.convBf16PackedBytes(const filters, K: SizeInt): SizeInt;
+var
+  n: int64;
+begin
+  { bytes of the packed bf16 weights of a filters x K matrix (K = c*size*size):
+    allocate them with createDeviceBuffer once per layer }
+  n := 0;
+  check(tns_conv_bf16_packed_bytes(FCtx, filters, K, @n));
+  result := n
+end;
+
+procedure TNNHip<T>.convBf16Pack(const filters, K: SizeInt; const weights: TCUMem; packedWeights: TCUMem);
+begin
+  { the layer's weights (batch norm folded) rounded to bf16 into the forward
+    kernel's layout, once after loading them }
+  check(tns_conv_bf16_pack(FCtx, filters, K, THipMem(weights), pointer(packedWeights)))
+end;
+
+procedure TNNHip<T>.convForwardBf16(const batch, C, H, W: SizeInt; const input, packedWeights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
+begin
+  { the convolutional layer's inference forward (dilation 1, folded biases) on
+    the bf16 MFMA: reduced precision, opt-in; input and output stay singles }
+  check(tns_conv_bf16_forward(FCtx, batch, C, H, W, THipMem(input), pointer(packedWeights),
+    THipMem(biases), filters, kSize, stride, padding, activation, THipMem(output)))
 end;
 
 procedure TNNHip<T>.imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64);

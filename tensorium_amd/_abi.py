@@ -39,6 +39,7 @@ TNS_OPT_DX_CONV = 11
 TNS_OPT_DW_RES = 12
 TNS_OPT_DERIVE_SUMS = 13
 TNS_OPT_SCRATCH_CAP = 14
+TNS_OPT_CONV_BF16_TILE = 15
 
 _CONV = [i64] * 11  # aChannels .. dilationX
 
@@ -257,6 +258,11 @@ PROTOTYPES.update({
                                   i32, f32, f32, f32, f32, f32, fptr, fptr, fptr, fptr]),
     "tns_region_detections": (C.c_int, [vp, i64, i64, i64, i64, i64, C.POINTER(f32), i32, i64, i64,
                                         i64, i64, f32, i32, i32, fptr, i64, vp, fptr, fptr, fptr]),
+    # the bf16 conv forward: packed an opaque device buffer, bytes a host int64
+    "tns_conv_bf16_packed_bytes": (C.c_int, [vp, i64, i64, C.POINTER(i64)]),
+    "tns_conv_bf16_pack": (C.c_int, [vp, i64, i64, fptr, vp]),
+    "tns_conv_bf16_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, vp, fptr, i64, i64, i64,
+                                        i64, i32, fptr]),
     # dropout (the seed an int64 in [0, 2^32)) and the elementwise loss heads
     "tns_hip_dropout_forward": (C.c_int, [vp, i64, i64, f32, f32, fptr, fptr, fptr]),
     "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),

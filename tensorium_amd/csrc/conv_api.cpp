@@ -180,6 +180,16 @@ ConvFwdPlan plan_conv_forward(const ConvShape& s, int fused, bool bias_act, cons
   return p;
 }
 
+// The bf16 forward's tile (conv_bf16.hip): the 128 x 128 tile where no row of
+// it is padding to speak of (filters >= 128) and it gives each of the 256 CUs
+// two blocks, else the 64 x 64 one (the 13^2 and 26^2 planes at the bench's
+// batch: N = 1352 and 5408 are 11 and 43 large column tiles).  Measured per
+// layer with each tile forced: profiles/conv_bf16_perf.json, DESIGN.md
+int conv_bf16_pick(int64_t filters, int64_t N, int64_t forced) {
+  if (forced >= 0) return (int)forced;
+  return filters >= 128 && ((filters + 127) / 128) * ((N + 127) / 128) >= 512 ? 0 : 1;
+}
+
 ConvBwdPlan plan_conv_backward(const ConvShape& s, bool has_bn, bool has_state_delta,
                                bool delta_aligned16, const Options& o) {
   ConvBwdPlan p;
@@ -1013,3 +1023,77 @@ int tns_conv_dx_conv_count(void) { return conv_tile4_dx3_count(); }
 int tns_conv_dw_res_count(void) { return dw_res_count(); }
 int tns_conv_dw_tile_count(void) { return dw_tile_count(); }
 const char* tns_conv_tile_variant_name(int32_t v) { return conv_tile_name(v); }
+
+// ---- bf16 convolution forward (conv_bf16.hip) ------------------------------------
+// Opt-in reduced-precision inference; no TNNCuda methods, hence no tns_hip_
+// prefix: the entries join the side stream on every call (check_ctx) instead
+// of taking a place in the hazard table
+namespace {
+int bf16_matrix(const char* what, int64_t filters, int64_t K) {
+  if (filters <= 0 || K <= 0 || filters > 0x0fffffffLL || K > 0x0fffffffLL - KTAB_PAD)
+    return set_error(TNS_ERR_ARG, "%s: filters %lld x K %lld outside [1, 2^28)", what,
+                     (long long)filters, (long long)K);
+  return TNS_OK;
+}
+}  // namespace
+
+int tns_conv_bf16_packed_bytes(tns_ctx* c, int64_t filters, int64_t K, int64_t* bytes) {
+  if (int r = check_ctx(c)) return r;
+  if (int r = bf16_matrix("conv bf16 packed bytes", filters, K)) return r;
+  if (!bytes) return set_error(TNS_ERR_ARG, "conv bf16 packed bytes: null bytes");
+  *bytes = conv_bf16_packed_bytes(filters, K);
+  return TNS_OK;
+}
+
+int tns_conv_bf16_pack(tns_ctx* c, int64_t filters, int64_t K, const float* weights,
+                       void* packed) {
+  if (int r = check_ctx(c)) return r;
+  if (int r = bf16_matrix("conv bf16 pack", filters, K)) return r;
+  if (!weights || !packed || !aligned16(packed))
+    return set_error(TNS_ERR_ARG, "conv bf16 pack: null operand, or packed not 16-byte aligned");
+  const Span a = span(weights, filters * K);
+  const Span b = span(static_cast<const float*>(packed), conv_bf16_packed_bytes(filters, K) / 4);
+  if (a.lo < b.hi && b.lo < a.hi)
+    return set_error(TNS_ERR_ARG, "conv bf16 pack: weights and packed overlap");
+  return hip_status(launch_conv_bf16_pack(filters, K, weights, packed, c->stream),
+                    "conv bf16 pack");
+}
+
+int tns_conv_bf16_forward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
+                          const float* input, const void* packed, const float* biases,
+                          int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
+                          int32_t activation, float* out) {
+  if (int r = check_ctx(c)) return r;
+  if (!act_supported(activation))
+    return set_error(TNS_ERR_UNSUPPORTED, "conv bf16 forward: activation %d not implemented",
+                     activation);
+  if (batch <= 0 || C <= 0 || H <= 0 || W <= 0 || filters <= 0 || kSize <= 0 || stride <= 0 ||
+      padding < 0)
+    return set_error(TNS_ERR_ARG, "conv bf16 forward: a size is not positive");
+  // the k-table's tap displacements and its sentinels (16384) must fall
+  // outside every window; offsets inside one image are 32-bit
+  if (H + padding >= 0x4000 || W + padding >= 0x4000 || kSize >= 0x4000 || stride >= 0x4000 ||
+      C > 0x0fffffffLL || C * H * W * 4 > 0x7fffffffLL || batch > 0x7fffffffLL)
+    return set_error(TNS_ERR_ARG, "conv bf16 forward: image, padding or kernel too large");
+  if (int r = bf16_matrix("conv bf16 forward", filters, C * kSize * kSize)) return r;
+  const int64_t oh = out_dim(H, padding, kSize, 1, stride);
+  const int64_t ow = out_dim(W, padding, kSize, 1, stride);
+  if (oh <= 0 || ow <= 0)
+    return set_error(TNS_ERR_ARG, "conv bf16 forward: the kernel exceeds the padded image");
+  if (filters * oh * ow > 0x7fffffffLL)
+    return set_error(TNS_ERR_ARG, "conv bf16 forward: an output image beyond 2^31 elements");
+  if (!input || !packed || !biases || !out || !aligned16(packed))
+    return set_error(TNS_ERR_ARG,
+                     "conv bf16 forward: null operand, or packed not 16-byte aligned");
+  const Span a = span(input, batch * C * H * W), b = span(out, batch * filters * oh * ow);
+  if (a.lo < b.hi && b.lo < a.hi)
+    return set_error(TNS_ERR_ARG, "conv bf16 forward: input and out overlap");
+  const int tile = conv_bf16_pick(filters, batch * oh * ow, g_opt.conv_bf16_tile);
+  ConvBf16Args v{};
+  if (int r = get_ktab(c, C, H, W, kSize, kSize, 1, 1, &v.ktab)) return r;
+  v.input = input, v.packed = packed, v.bias = biases, v.out = out;
+  v.batch = batch, v.C = C, v.H = H, v.W = W, v.filters = filters, v.ks = kSize;
+  v.stride = stride, v.pad = padding, v.oh = oh, v.ow = ow, v.act = activation;
+  OpTimer t(c, TNS_OP_GEMM);
+  return hip_status(launch_conv_bf16(tile, v, c->stream), "conv bf16 forward");
+}

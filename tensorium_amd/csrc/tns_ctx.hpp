@@ -91,6 +91,8 @@ struct Options {
   int64_t srss_quirk = 0;
   int64_t conv_variant = -1;
   int64_t conv_pad = -1;
+  // TNS_OPT_CONV_BF16_TILE: -1 the planner's tile (conv_bf16_pick), v >= 0 tile v
+  int64_t conv_bf16_tile = -1;
 };
 extern Options g_opt;  // (tns_api.cpp)
 

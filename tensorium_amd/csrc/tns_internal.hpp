@@ -650,4 +650,28 @@ struct ConvBwdPlan {
 ConvBwdPlan plan_conv_backward(const ConvShape& s, bool has_bn, bool has_state_delta,
                                bool delta_aligned16, const Options& o);
 
+// ---- bf16 conv forward (conv_bf16.hip) -----------------------------------------
+// The opt-in reduced-precision inference path: weights packed once as bf16 in
+// the kernel's A-fragment order, pixels gathered from the fp32 images and
+// rounded in registers, fp32 accumulators, fp32 bias / activation / output.
+// Tile v of conv_bf16_tile_count(): 0 = 128 x 128, 1 = 64 x 64 (filters x
+// columns).  conv_bf16_pick: the planner, a pure function of the GEMM's extent
+// and TNS_OPT_CONV_BF16_TILE (forced >= 0 names the tile).
+struct ConvBf16Args {
+  const float* input;  // [batch][C][H][W]
+  const void* packed;  // conv_bf16_packed_bytes(filters, C*ks*ks) bytes
+  const float* bias;   // [filters]
+  float* out;          // [batch][filters][oh*ow]
+  const int* ktab;     // get_ktab(C, H, W, ks, ks, 1, 1)
+  int64_t batch, C, H, W, filters, ks, stride, pad, oh, ow;
+  int act;
+};
+int conv_bf16_tile_count();
+const char* conv_bf16_tile_name(int v);
+int conv_bf16_pick(int64_t filters, int64_t N, int64_t forced);
+int64_t conv_bf16_packed_bytes(int64_t filters, int64_t K);
+hipError_t launch_conv_bf16_pack(int64_t filters, int64_t K, const float* weights, void* packed,
+                                 hipStream_t s);
+hipError_t launch_conv_bf16(int tile, const ConvBf16Args& c, hipStream_t s);
+
 }  // namespace tns

@@ -242,14 +242,29 @@ class HipDarknet(_Driver):
     by the rolling statistics.  An rnn layer (``_RnnLayers``) likewise carries
     its ``state``: with time_steps = 1 from call to call; with more, step i of
     a call reads what step i of the call before left (the reference's
-    inference does not chain the steps of one call)."""
+    inference does not chain the steps of one call).
+
+    ``precision="bf16"`` (opt-in; the default "fp32" is the bit-exact path)
+    packs every convolutional layer's folded weights as bf16 once and runs
+    those layers through ``convForwardBf16``: bf16 operands, fp32
+    accumulation, bias, activation and output.  Every other layer, and every
+    buffer, is as in fp32; the outputs are close to, not equal to, the fp32
+    path's."""
+
+    PRECISIONS = ("fp32", "bf16")
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch,
-                 lstm_fused: bool = True, rnn_fused: bool = True):
+                 lstm_fused: bool = True, rnn_fused: bool = True, precision: str = "fp32"):
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {self.PRECISIONS}")
+        self.precision = precision
         self.conv_params = {}
         for l, p in self._build(hip, net, params, torch, lstm_fused, rnn_fused, training=False):
             f = fuse_batchnorm(l, p)
-            self.conv_params[l.index] = (self._t(f.weights), self._t(f.biases))
+            w = self._t(f.weights)
+            if precision == "bf16":  # packed once; the fp32 copy is dropped
+                w = hip.convBf16Pack(l.filters, l.c * l.size * l.size, w)
+            self.conv_params[l.index] = (w, self._t(f.biases))
 
     def forward(self, x):
         """x: device tensor [batch, c, h, w] (contiguous).  Returns the per-
@@ -261,8 +276,12 @@ class HipDarknet(_Driver):
             out = self.out[l.index]
             if l.kind == "convolutional":
                 w, b = self.conv_params[l.index]
-                hip.convForward(B, l.c, l.h, l.w, prev, w, b, l.filters, l.size, l.stride, l.pad,
-                                1, l.activation, None, out, fused=True)
+                if self.precision == "bf16":
+                    hip.convForwardBf16(B, l.c, l.h, l.w, prev, w, b, l.filters, l.size,
+                                        l.stride, l.pad, l.activation, out)
+                else:
+                    hip.convForward(B, l.c, l.h, l.w, prev, w, b, l.filters, l.size, l.stride,
+                                    l.pad, 1, l.activation, None, out, fused=True)
             elif l.kind == "maxpool":  # inference: no indexes
                 hip.forwardMaxPool(B, l.out_c, l.out_h, l.out_w, prev, l.c, l.h, l.w, l.stride_x,
                                    l.stride_y, l.pad, l.size, None, out)

@@ -56,6 +56,17 @@ def _iptr(x):
     raise TnsError(f"unsupported buffer type {type(x)!r}")
 
 
+def _bptr(x):
+    """An opaque byte buffer (the packed bf16 weights)."""
+    if x is None or isinstance(x, int):
+        return x
+    if torch is not None and isinstance(x, torch.Tensor):
+        if not x.is_cuda or x.dtype != torch.uint8 or not x.is_contiguous():
+            raise TnsError("TNNHip expects a contiguous device (cuda) uint8 tensor")
+        return x.data_ptr()
+    raise TnsError(f"unsupported buffer type {type(x)!r}")
+
+
 class TNNHip:
     """HIP twin of TNNCuda<single> (one context = one device + one stream)."""
 
@@ -460,6 +471,32 @@ class TNNHip:
                                             padding, dilation, int(activation), _ptr(workspace),
                                             _ptr(out), mode))
 
+    # the opt-in reduced-precision inference path (tns_conv_bf16_*): not bit-exact
+    def convBf16PackedBytes(self, filters, K) -> int:
+        """Bytes of the packed bf16 weight buffer of a filters x K matrix."""
+        n = C.c_int64()
+        check(self.lib.tns_conv_bf16_packed_bytes(self.ctx, filters, K, C.byref(n)))
+        return int(n.value)
+
+    def convBf16Pack(self, filters, K, weights, packed=None):
+        """weights [filters][K] (device float32) rounded to bf16 into the
+        forward kernel's layout.  packed: a device uint8 tensor of
+        convBf16PackedBytes(filters, K) bytes or a raw pointer; allocated when
+        None.  Returns packed."""
+        if packed is None:
+            packed = torch.empty(self.convBf16PackedBytes(filters, K), dtype=torch.uint8,
+                                 device=weights.device)
+        check(self.lib.tns_conv_bf16_pack(self.ctx, filters, K, _ptr(weights), _bptr(packed)))
+        return packed
+
+    def convForwardBf16(self, batch, C_, H, W, input, packed, biases, filters, kSize, stride,
+                        padding, activation, out):
+        """convForward at dilation 1 on the bf16 MFMA: fp32 input, biases and
+        out, weights as convBf16Pack left them."""
+        check(self.lib.tns_conv_bf16_forward(self.ctx, batch, C_, H, W, _ptr(input), _bptr(packed),
+                                             _ptr(biases), filters, kSize, stride, padding,
+                                             int(activation), _ptr(out)))
+
     def convBackward(self, batch, C_, H, W, input, weights, filters, kSize, stride, padding,
                      dilation, activation, output, delta, bias_updates, weight_updates,
                      workspace=None, state_delta=None):
@@ -568,6 +605,11 @@ class TNNHip:
         """Largest context scratch buffer in floats (0 = none); a larger
         request fails as a failed allocation does; process-wide."""
         check(self.lib.tns_set_option(14, int(floats)))
+
+    def setConvBf16Tile(self, tile: int = -1):
+        """convForwardBf16's tile: -1 by shape, 0 the 128 x 128 tile, 1 the
+        64 x 64 one; every tile takes every shape; process-wide."""
+        check(self.lib.tns_set_option(15, int(tile)))
 
     def setDeriveSums(self, on: bool = False):
         """Conv backward (no batch norm): Derivative fused into addSums'
