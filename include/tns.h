@@ -651,6 +651,42 @@ int tns_conv_bf16_forward(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int
                           int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
                           int32_t activation, float* out);
 
+/* ---- bf16 convolution backward, opt-in reduced-precision training (conv_bf16_bwd.hip) ----
+ * tns_conv_bf16_backward[_bn]: operands and meaning of tns_hip_conv_backward[_bn]
+ * at dilation 1, without a workspace.  The delta preparation (Derivative, then
+ * the bias sums or batchNormBack) is that call's own, fp32 and bit for bit; the
+ * two products then run on the bf16 MFMA, on the context's stream:
+ *   weight_updates += sum_b delta_b . col_b^T            (dW)
+ *   state_delta    += col2im(W^T . delta_b)              (dX, state_delta != NULL)
+ * with delta, input and weights (plain fp32 [filters][C*kSize*kSize]) rounded
+ * to bf16 (nearest even) on their way in, products exact in fp32, fp32
+ * accumulation and an fp32 add into the buffer.  Not bit-exact against the fp32
+ * calls: an element lies within (n + 2) * 2^-23 * S + 2^-23 of the exact sum of
+ * the rounded operands' products plus the prior value, S the same sum over
+ * absolute values, n = batch*oh*ow for dW and filters*kSize*kSize for dX.
+ * Deterministic: no atomics, the same call gives the same bits.  Scratch (the
+ * packed W^T, dW's partial sums) is the context's.  TNS_ERR_UNSUPPORTED: an
+ * activation the library does not implement.  TNS_ERR_ARG, nothing launched or
+ * written: a null operand (state_delta excepted), a non-positive size, an empty
+ * output, the sizes tns_conv_bf16_forward refuses, batch*oh*ow beyond 2^31, and
+ * weight_updates, state_delta or delta overlapping another operand.
+ * TNS_OPT_CONV_BF16_TILE also forces dX's tile.  TNS_OPT_CONV_BF16_DW_SPLIT
+ * (default -1: by shape; v >= 1: v slices, clamped to the reduction's steps of
+ * 32) sets into how many contiguous slices dW's reduction over batch*oh*ow is
+ * cut; their fp32 partial results are added in slice order. */
+int tns_conv_bf16_backward(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int64_t W,
+                           const float* input, const float* weights, int64_t filters,
+                           int64_t kSize, int64_t stride, int64_t padding, int32_t activation,
+                           const float* output, float* delta, float* bias_updates,
+                           float* weight_updates, float* state_delta);
+int tns_conv_bf16_backward_bn(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int64_t W,
+                              const float* input, const float* weights, int64_t filters,
+                              int64_t kSize, int64_t stride, int64_t padding, int32_t activation,
+                              const float* output, float* delta, const float* scales,
+                              const float* x, const float* x_norm, const float* mean,
+                              const float* variance, float* scale_updates, float* mean_delta,
+                              float* variance_delta, float* weight_updates, float* state_delta);
+
 /* ---- dropout and the elementwise loss heads (heads.hip) ----
  * tns_hip_dropout_forward = TNNCuda.forwardDropout, the reference's device
  * kernel (cuda_sgemm.cu:1617-1645), a pure function of (seed, i) — the CPU
@@ -1124,7 +1160,7 @@ enum { TNS_OPT_STRICT_BETA0 = 0, TNS_OPT_CONV_VARIANT = 1, TNS_OPT_CONV_PAD = 2,
        TNS_OPT_SDOT_FORM = 6, TNS_OPT_DX_FUSED = 7, TNS_OPT_DX_TILE = 8,
        TNS_OPT_DW_TILE = 9, TNS_OPT_BWD_OVERLAP = 10, TNS_OPT_DX_CONV = 11,
        TNS_OPT_DW_RES = 12, TNS_OPT_DERIVE_SUMS = 13, TNS_OPT_SCRATCH_CAP = 14,
-       TNS_OPT_CONV_BF16_TILE = 15 };
+       TNS_OPT_CONV_BF16_TILE = 15, TNS_OPT_CONV_BF16_DW_SPLIT = 16 };
 int tns_set_option(int32_t opt, int64_t value);
 
 #ifdef __cplusplus

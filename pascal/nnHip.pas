@@ -67,6 +67,7 @@ const
   TNS_OPT_DERIVE_SUMS = 13;
   TNS_OPT_SCRATCH_CAP = 14;
   TNS_OPT_CONV_BF16_TILE = 15;
+  TNS_OPT_CONV_BF16_DW_SPLIT = 16;
 
 type
   PTnsCtx = pointer;
@@ -263,6 +264,15 @@ function tns_conv_bf16_pack(ctx: PTnsCtx; filters, K: int64; weights: THipMem;
 function tns_conv_bf16_forward(ctx: PTnsCtx; batch, C, H, W: int64; input: THipMem;
   packedWeights: pointer; biases: THipMem; filters, kSize, stride, padding: int64;
   activation: longint; output: THipMem): longint; cdecl; external libtns;
+{ the opt-in bf16 convolution backward (conv_bf16_bwd.hip): tns_hip_conv_backward[_bn] at
+  dilation 1 with dW and state.delta on the bf16 MFMA; plain single weights, no workspace }
+function tns_conv_bf16_backward(ctx: PTnsCtx; batch, C, H, W: int64; input, weights: THipMem;
+  filters, kSize, stride, padding: int64; activation: longint; output, delta, biasUpdates,
+  weightUpdates, stateDelta: THipMem): longint; cdecl; external libtns;
+function tns_conv_bf16_backward_bn(ctx: PTnsCtx; batch, C, H, W: int64; input, weights: THipMem;
+  filters, kSize, stride, padding: int64; activation: longint; output, delta, scales, x, xNorm,
+  mean, variance, scaleUpdates, meanDelta, varianceDelta, weightUpdates,
+  stateDelta: THipMem): longint; cdecl; external libtns;
 
 { dropout (seed in [0, 2^32)) and the elementwise loss heads }
 function tns_hip_dropout_forward(ctx: PTnsCtx; N, seed: int64; probability, scale: single; src,
@@ -444,6 +454,8 @@ type
     function convBf16PackedBytes(const filters, K: SizeInt): SizeInt;
     procedure convBf16Pack(const filters, K: SizeInt; const weights: TCUMem; packedWeights: TCUMem);
     procedure convForwardBf16(const batch, C, H, W: SizeInt; const input, packedWeights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
+    procedure convBackwardBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta, biasUpdates, weightUpdates, stateDelta: TCUMem);
+    procedure convBackwardBNBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta: TCUMem; const scales, x, xNorm, mean, variance: TCUMem; scaleUpdates, meanDelta, varianceDelta, weightUpdates, stateDelta: TCUMem);
     procedure imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64 = nil);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
@@ -820,6 +832,26 @@ begin
     the bf16 MFMA: reduced precision, opt-in; input and output stay singles }
   check(tns_conv_bf16_forward(FCtx, batch, C, H, W, THipMem(input), pointer(packedWeights),
     THipMem(biases), filters, kSize, stride, padding, activation, THipMem(output)))
+end;
+
+procedure TNNHip<T>.convBackwardBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta, biasUpdates, weightUpdates, stateDelta: TCUMem);
+begin
+  { the convolutional layer's backward without batch norm (dilation 1): the delta
+    preparation as convBackward's, dW and state.delta (nil: none) on the bf16
+    MFMA: reduced precision, opt-in; every buffer stays singles }
+  check(tns_conv_bf16_backward(FCtx, batch, C, H, W, THipMem(input), THipMem(weights), filters,
+    kSize, stride, padding, activation, THipMem(output), THipMem(delta), THipMem(biasUpdates),
+    THipMem(weightUpdates), THipMem(stateDelta)))
+end;
+
+procedure TNNHip<T>.convBackwardBNBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta: TCUMem; const scales, x, xNorm, mean, variance: TCUMem; scaleUpdates, meanDelta, varianceDelta, weightUpdates, stateDelta: TCUMem);
+begin
+  { the same for a batch-normalized layer: batchNormBack as convBackwardBN's }
+  check(tns_conv_bf16_backward_bn(FCtx, batch, C, H, W, THipMem(input), THipMem(weights),
+    filters, kSize, stride, padding, activation, THipMem(output), THipMem(delta),
+    THipMem(scales), THipMem(x), THipMem(xNorm), THipMem(mean), THipMem(variance),
+    THipMem(scaleUpdates), THipMem(meanDelta), THipMem(varianceDelta), THipMem(weightUpdates),
+    THipMem(stateDelta)))
 end;
 
 procedure TNNHip<T>.imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64);

@@ -40,6 +40,7 @@ TNS_OPT_DW_RES = 12
 TNS_OPT_DERIVE_SUMS = 13
 TNS_OPT_SCRATCH_CAP = 14
 TNS_OPT_CONV_BF16_TILE = 15
+TNS_OPT_CONV_BF16_DW_SPLIT = 16
 
 _CONV = [i64] * 11  # aChannels .. dilationX
 
@@ -263,6 +264,12 @@ PROTOTYPES.update({
     "tns_conv_bf16_pack": (C.c_int, [vp, i64, i64, fptr, vp]),
     "tns_conv_bf16_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, vp, fptr, i64, i64, i64,
                                         i64, i32, fptr]),
+    # the bf16 conv backward: tns_hip_conv_backward[_bn] without dilation and workspace
+    "tns_conv_bf16_backward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64, i64,
+                                         i32, fptr, fptr, fptr, fptr, fptr]),
+    "tns_conv_bf16_backward_bn": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64,
+                                            i64, i32, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                            fptr, fptr, fptr, fptr, fptr]),
     # dropout (the seed an int64 in [0, 2^32)) and the elementwise loss heads
     "tns_hip_dropout_forward": (C.c_int, [vp, i64, i64, f32, f32, fptr, fptr, fptr]),
     "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),

@@ -190,6 +190,26 @@ int conv_bf16_pick(int64_t filters, int64_t N, int64_t forced) {
   return filters >= 128 && ((filters + 127) / 128) * ((N + 127) / 128) >= 512 ? 0 : 1;
 }
 
+// The bf16 dW's tile (conv_bf16_bwd.hip): 128 x 128 where neither side of the
+// filters x K output is mostly padding in it, else 64 x 64
+int conv_bf16_dw_tile(int64_t filters, int64_t K) { return filters >= 128 && K >= 128 ? 0 : 1; }
+
+// ... and the slices of its reduction over R = batch * oh * ow (steps of 32):
+// enough of them that the tiles x slices give each of the 256 CUs two blocks,
+// none shorter than eight steps, and the fp32 partials [S][filters][K] within
+// TNS_OPT_SCRATCH_CAP (cap > 0, in floats).  forced >= 1 names the count; the
+// result is clamped to the steps and normalised so that no slice is empty
+int64_t conv_bf16_dw_split(int64_t filters, int64_t K, int64_t R, int64_t forced, int64_t cap) {
+  const int64_t bt = conv_bf16_dw_tile(filters, K) == 0 ? 128 : 64;
+  const int64_t tiles = ((filters + bt - 1) / bt) * ((K + bt - 1) / bt);
+  const int64_t steps = std::max<int64_t>(1, (R + 31) / 32);
+  int64_t S = forced >= 1 ? forced : std::min((512 + tiles - 1) / tiles, steps / 8);
+  if (cap > 0) S = std::min(S, cap / (filters * K));
+  S = std::max<int64_t>(1, std::min(S, steps));
+  const int64_t per = (steps + S - 1) / S;
+  return (steps + per - 1) / per;
+}
+
 ConvBwdPlan plan_conv_backward(const ConvShape& s, bool has_bn, bool has_state_delta,
                                bool delta_aligned16, const Options& o) {
   ConvBwdPlan p;
@@ -1096,4 +1116,118 @@ int tns_conv_bf16_forward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64
   v.stride = stride, v.pad = padding, v.oh = oh, v.ow = ow, v.act = activation;
   OpTimer t(c, TNS_OP_GEMM);
   return hip_status(launch_conv_bf16(tile, v, c->stream), "conv bf16 forward");
+}
+
+// ---- bf16 convolution backward (conv_bf16_bwd.hip) ---------------------------------
+// Opt-in reduced-precision training: the fp32 delta preparation of
+// tns_hip_conv_backward[_bn] (run_bwd_prologue), then dW and dX on the bf16
+// MFMA, all on the context's stream
+namespace {
+bool meet(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+int conv_bf16_backward(tns_ctx* c, const ConvShape& s, const ConvBwdOps& o) {
+  const char* const me = "conv bf16 backward";
+  if (!c) return check_ctx(c);
+  const ConvBN& bn = o.bn;
+  if (!act_supported(s.activation))
+    return set_error(TNS_ERR_UNSUPPORTED, "%s: activation %d not implemented", me, s.activation);
+  if (s.batch <= 0 || s.C <= 0 || s.H <= 0 || s.W <= 0 || s.filters <= 0 || s.kSize <= 0 ||
+      s.stride <= 0 || s.padding < 0)
+    return set_error(TNS_ERR_ARG, "%s: a size is not positive", me);
+  // the k-tables' tap displacements and sentinels (16384) must fall outside
+  // every window; offsets inside one image are 32-bit
+  if (s.H + s.padding >= 0x4000 || s.W + s.padding >= 0x4000 || s.kSize >= 0x4000 ||
+      s.stride >= 0x4000 || s.C > 0x0fffffffLL || s.C * s.H * s.W * 4 > 0x7fffffffLL ||
+      s.batch > 0x7fffffffLL)
+    return set_error(TNS_ERR_ARG, "%s: image, padding or kernel too large", me);
+  const int64_t kk = s.kSize * s.kSize, K = s.C * kk, Kd = s.filters * kk;
+  if (int r = bf16_matrix(me, s.filters, K)) return r;
+  if (int r = bf16_matrix(me, s.C, Kd)) return r;
+  const int64_t oh = out_dim(s.H, s.padding, s.kSize, 1, s.stride);
+  const int64_t ow = out_dim(s.W, s.padding, s.kSize, 1, s.stride);
+  if (oh <= 0 || ow <= 0)
+    return set_error(TNS_ERR_ARG, "%s: the kernel exceeds the padded image", me);
+  const int64_t R = s.batch * oh * ow;
+  if (s.filters * oh * ow * 4 > 0x7fffffffLL || R > 0x7fffff00LL)
+    return set_error(TNS_ERR_ARG, "%s: a delta image or the reduction beyond 32-bit indexing", me);
+  if (!o.input || !o.weights || !o.output || !o.delta || !o.weight_updates ||
+      (!bn.scales && !o.bias_updates))
+    return set_error(TNS_ERR_ARG, "%s: null operand", me);
+  if (bn.scales && (!bn.x || !bn.x_norm || !bn.mean || !bn.variance || !bn.scale_updates ||
+                    !bn.mean_delta || !bn.variance_delta))
+    return set_error(TNS_ERR_ARG, "%s: null batch-norm operand", me);
+  const int64_t nin = s.batch * s.C * s.H * s.W, nd = s.batch * s.filters * oh * ow;
+  const Span si = span(o.input, nin), sw = span(o.weights, s.filters * K), sd = span(o.delta, nd),
+             swu = span(o.weight_updates, s.filters * K), ssd = span(o.state_delta, nin);
+  if (meet(ssd, sd) || meet(ssd, sw) || meet(ssd, swu) || meet(swu, sd) || meet(swu, sw) ||
+      meet(swu, si) || meet(sd, si) || meet(sd, sw))
+    return set_error(TNS_ERR_ARG, "%s: an updated buffer overlaps another operand", me);
+  const ConvBwdPlan p = plan_conv_backward(s, bn.scales != nullptr, o.state_delta != nullptr,
+                                           aligned16(o.delta), g_opt);
+  if (p.err) return set_error(p.err, "%s", p.msg);
+  // a pending pipelined fp32 dW may still read delta or input, or write
+  // weight_updates: joined where this call's operands meet its
+  const int64_t nf = bn.scales ? s.filters : 0;
+  if (int e = check_ops(c,
+                        {sd, ssd, swu, span(o.bias_updates, bn.scales ? 0 : s.filters),
+                         span(bn.scale_updates, nf), span(bn.mean_delta, nf),
+                         span(bn.variance_delta, nf)},
+                        {si, sw, span(o.output, nd), span(bn.x, nf ? nd : 0),
+                         span(bn.x_norm, nf ? nd : 0), span(bn.scales, nf), span(bn.mean, nf),
+                         span(bn.variance, nf)}))
+    return e;
+  // every scratch buffer and table before the first launch that writes an operand
+  const int split = (int)conv_bf16_dw_split(s.filters, K, R, g_opt.conv_bf16_dw_split,
+                                            g_opt.scratch_cap);
+  ConvBf16BwdArgs v{};
+  float *part = nullptr, *wt = nullptr;
+  if (int e = ensure_scratch(c, SLOT_BN, p.bn_elems, &part)) return e;
+  if (split > 1)
+    if (int e = ensure_scratch(c, SLOT_BF16_DW, split * s.filters * K, &v.dw_part)) return e;
+  if (int e = get_ktab(c, s.C, s.H, s.W, s.kSize, s.kSize, 1, 1, &v.ktab_in)) return e;
+  if (o.state_delta) {
+    if (int e = ensure_scratch(c, SLOT_BF16_WT, conv_bf16_packed_bytes(s.C, Kd) / 4, &wt))
+      return e;
+    if (int e = get_ktab(c, s.filters, oh, ow, s.kSize, s.kSize, 1, 1, &v.ktab_delta)) return e;
+  }
+  if (int e = run_bwd_prologue(c, p, o, part)) return e;
+  v.input = o.input, v.weights = o.weights, v.delta = o.delta;
+  v.weight_updates = o.weight_updates, v.state_delta = o.state_delta, v.packed_wt = wt;
+  v.batch = s.batch, v.C = s.C, v.H = s.H, v.W = s.W, v.filters = s.filters, v.ks = s.kSize;
+  v.stride = s.stride, v.pad = s.padding, v.oh = oh, v.ow = ow;
+  {
+    OpTimer t(c, TNS_OP_GEMM);
+    if (int e = hip_status(launch_conv_bf16_dw(split, v, c->stream), "conv bf16 dW")) return e;
+  }
+  if (!o.state_delta) return TNS_OK;
+  const int tile = conv_bf16_pick(s.C, s.batch * s.H * s.W, g_opt.conv_bf16_tile);
+  OpTimer t(c, TNS_OP_GEMM);
+  return hip_status(launch_conv_bf16_dx(tile, v, c->stream), "conv bf16 dX");
+}
+}  // namespace
+
+int tns_conv_bf16_backward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
+                           const float* input, const float* weights, int64_t filters,
+                           int64_t kSize, int64_t stride, int64_t padding, int32_t activation,
+                           const float* output, float* delta, float* bias_updates,
+                           float* weight_updates, float* state_delta) {
+  return conv_bf16_backward(
+      c, ConvShape{batch, C, H, W, filters, kSize, stride, padding, 1, activation, false},
+      ConvBwdOps{input, weights, output, delta, bias_updates, weight_updates, nullptr,
+                 state_delta, ConvBN{}});
+}
+
+int tns_conv_bf16_backward_bn(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
+                              const float* input, const float* weights, int64_t filters,
+                              int64_t kSize, int64_t stride, int64_t padding, int32_t activation,
+                              const float* output, float* delta, const float* scales,
+                              const float* x, const float* x_norm, const float* mean,
+                              const float* variance, float* scale_updates, float* mean_delta,
+                              float* variance_delta, float* weight_updates, float* state_delta) {
+  if (!scales) return set_error(TNS_ERR_ARG, "conv bf16 backward_bn: null scales");
+  ConvBN bn{scales, x, x_norm, mean, variance, scale_updates, mean_delta, variance_delta};
+  return conv_bf16_backward(
+      c, ConvShape{batch, C, H, W, filters, kSize, stride, padding, 1, activation, false},
+      ConvBwdOps{input, weights, output, delta, nullptr, weight_updates, nullptr, state_delta,
+                 bn});
 }

@@ -47,20 +47,13 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
+#include "conv_bf16_common.hpp"
 #include "tns_act.hpp"
 
 namespace tns {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kStep = 32;       // k per LDS stage
-constexpr int kRow = 80;        // LDS bytes per pixel row: 64 of data, 16 of padding
-constexpr int kPackRows = 128;  // filters are padded to the tallest tile
-constexpr int kThreads = 256;
+using namespace bf16k;
 
 struct Bf16Args {
   const float* in;
@@ -72,14 +65,6 @@ struct Bf16Args {
   int ktab_n, H, W, ow, ohw, stride, pad, filters, act;
   int steps, ks16, mtiles;  // K / 32, K / 16 (padded K), tiles over the filters
 };
-
-// float to bf16, nearest even, Inf kept, NaN kept (quiet): the integer form,
-// whatever the denormal mode
-__device__ __forceinline__ unsigned bf16_rne(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // one thread per 16-byte piece of the packed buffer
 __global__ void __launch_bounds__(kThreads)
@@ -119,20 +104,6 @@ __device__ __forceinline__ void gather(const Bf16Args& a, const Column& c, int k
     const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
     const float x = c.img[ok ? c.pix + (off >> 2) : 0];
     g[i] = ok ? x : 0.0f;
-  }
-}
-
-template <int KPT>
-__device__ __forceinline__ void store_b(unsigned char* row, const float (&g)[KPT]) {
-#pragma unroll
-  for (int q = 0; q < KPT / 8; ++q) {
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2 p = {g[8 * q + 2 * j], g[8 * q + 2 * j + 1]};
-      w[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
-    }
-    reinterpret_cast<uint4*>(row)[q] = make_uint4(w[0], w[1], w[2], w[3]);
   }
 }
 

@@ -424,6 +424,9 @@ int tns_set_option(int32_t opt, int64_t value) {
         return set_error(TNS_ERR_ARG, "no bf16 conv tile %lld", (long long)value);
       g_opt.conv_bf16_tile = value < 0 ? -1 : value;
       return TNS_OK;
+    case TNS_OPT_CONV_BF16_DW_SPLIT:
+      g_opt.conv_bf16_dw_split = value < 1 ? -1 : value;
+      return TNS_OK;
     default:
       return set_error(TNS_ERR_ARG, "unknown option %d", opt);
   }

@@ -674,4 +674,30 @@ hipError_t launch_conv_bf16_pack(int64_t filters, int64_t K, const float* weight
                                  hipStream_t s);
 hipError_t launch_conv_bf16(int tile, const ConvBf16Args& c, hipStream_t s);
 
+// ---- bf16 conv backward (conv_bf16_bwd.hip) --------------------------------------
+// The opt-in reduced-precision training path: dW and dX of a layer on the bf16
+// MFMA from the fp32 buffers, fp32 accumulators, added to the fp32
+// weight_updates / state_delta.  dX takes the forward's tiles (conv_bf16_pick
+// over C x batch*H*W); dW's tile is conv_bf16_dw_tile (0 = 128 x 128, 1 =
+// 64 x 64 over filters x K) and its reduction over R = batch*oh*ow is cut into
+// conv_bf16_dw_split slices: both pure functions of the extents,
+// TNS_OPT_CONV_BF16_DW_SPLIT (forced >= 1 names the slice count) and
+// TNS_OPT_SCRATCH_CAP (cap > 0: the partials [S][filters][K] stay within it).
+struct ConvBf16BwdArgs {
+  const float* input;     // [batch][C][H][W]
+  const float* weights;   // [filters][C*ks*ks]
+  const float* delta;     // [batch][filters][oh*ow]
+  float* weight_updates;  // [filters][C*ks*ks]
+  float* state_delta;     // [batch][C][H][W] (dX only)
+  void* packed_wt;        // dX: conv_bf16_packed_bytes(C, filters*ks*ks) bytes
+  float* dw_part;         // dW with S > 1 slices: S * filters * C*ks*ks floats
+  const int* ktab_in;     // dW: get_ktab(C, H, W, ks, ks, 1, 1)
+  const int* ktab_delta;  // dX: get_ktab(filters, oh, ow, ks, ks, 1, 1)
+  int64_t batch, C, H, W, filters, ks, stride, pad, oh, ow;
+};
+int conv_bf16_dw_tile(int64_t filters, int64_t K);
+int64_t conv_bf16_dw_split(int64_t filters, int64_t K, int64_t R, int64_t forced, int64_t cap);
+hipError_t launch_conv_bf16_dx(int tile, const ConvBf16BwdArgs& c, hipStream_t s);
+hipError_t launch_conv_bf16_dw(int split, const ConvBf16BwdArgs& c, hipStream_t s);
+
 }  // namespace tns

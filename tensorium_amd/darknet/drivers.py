@@ -458,13 +458,25 @@ class HipDarknetTrain(_Driver):
     for an lstm layer on its eight sub-layers in the order wf wi wg wo uf ui
     ug uo, for an rnn layer on input, self, output.  lstm layers:
     ``_LstmLayers``; rnn layers: ``_RnnLayers``; ``lstm_fused=False`` /
-    ``rnn_fused=False`` select the reference's call sequence, call for call."""
+    ``rnn_fused=False`` select the reference's call sequence, call for call.
+
+    ``precision="bf16"`` (opt-in; the default "fp32" is the bit-exact path)
+    sends every convolutional layer's backward through ``convBackwardBf16`` /
+    ``convBackwardBNBf16``: the delta preparation stays fp32, dW and
+    state.delta run on the bf16 MFMA with fp32 accumulation into the fp32
+    buffers.  The training forward, the connected and recurrent layers and
+    ``update`` stay fp32 (a bf16 training forward is the follow-up), so only
+    weight_updates and the deltas below a convolution differ from fp32's."""
 
     LOSS_KINDS = ("softmax", "cost", "logistic")
+    PRECISIONS = HipDarknet.PRECISIONS
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
                  seed: int = 0, lstm_fused: bool = True, rnn_fused: bool = True,
-                 yolo_loss: bool = False):
+                 yolo_loss: bool = False, precision: str = "fp32"):
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {self.PRECISIONS}")
+        self.precision = precision
         self.loss_scale = float(loss_scale)
         self.yolo_loss = bool(yolo_loss)
         yolos = net.yolos()
@@ -693,7 +705,16 @@ class HipDarknetTrain(_Driver):
             d = self.delta[i]
             if l.kind == "convolutional":
                 st = self.conv[i]
-                if l.bn:
+                if self.precision == "bf16" and l.bn:
+                    hip.convBackwardBNBf16(B, l.c, l.h, l.w, inp, st["w"], l.filters, l.size,
+                                           l.stride, l.pad, l.activation, self.out[i], d,
+                                           st["scales"], st["x"], st["xn"], st["mean"], st["var"],
+                                           st["su"], st["md"], st["vd"], st["wu"], sd)
+                elif self.precision == "bf16":
+                    hip.convBackwardBf16(B, l.c, l.h, l.w, inp, st["w"], l.filters, l.size,
+                                         l.stride, l.pad, l.activation, self.out[i], d, st["bu"],
+                                         st["wu"], sd)
+                elif l.bn:
                     hip.convBackwardBN(B, l.c, l.h, l.w, inp, st["w"], l.filters, l.size,
                                        l.stride, l.pad, 1, l.activation, self.out[i], d,
                                        st["scales"], st["x"], st["xn"], st["mean"], st["var"],

@@ -527,6 +527,30 @@ class TNNHip:
             _ptr(x_norm), _ptr(mean), _ptr(variance), _ptr(scale_updates), _ptr(mean_delta),
             _ptr(variance_delta), _ptr(weight_updates), _ptr(workspace), _ptr(state_delta)))
 
+    # the opt-in reduced-precision training path (tns_conv_bf16_backward*): not bit-exact
+    def convBackwardBf16(self, batch, C_, H, W, input, weights, filters, kSize, stride, padding,
+                         activation, output, delta, bias_updates, weight_updates,
+                         state_delta=None):
+        """convBackward at dilation 1 with dW and state_delta on the bf16 MFMA:
+        every buffer fp32 (weights plain [filters][K]), delta prepared in place
+        as convBackward does, no workspace."""
+        check(self.lib.tns_conv_bf16_backward(
+            self.ctx, batch, C_, H, W, _ptr(input), _ptr(weights), filters, kSize, stride,
+            padding, int(activation), _ptr(output), _ptr(delta), _ptr(bias_updates),
+            _ptr(weight_updates), _ptr(state_delta)))
+
+    def convBackwardBNBf16(self, batch, C_, H, W, input, weights, filters, kSize, stride,
+                           padding, activation, output, delta, scales, x, x_norm, mean, variance,
+                           scale_updates, mean_delta, variance_delta, weight_updates,
+                           state_delta=None):
+        """convBackwardBN likewise: batchNormBack in fp32, dW and state_delta
+        on the bf16 MFMA."""
+        check(self.lib.tns_conv_bf16_backward_bn(
+            self.ctx, batch, C_, H, W, _ptr(input), _ptr(weights), filters, kSize, stride, padding,
+            int(activation), _ptr(output), _ptr(delta), _ptr(scales), _ptr(x), _ptr(x_norm),
+            _ptr(mean), _ptr(variance), _ptr(scale_updates), _ptr(mean_delta),
+            _ptr(variance_delta), _ptr(weight_updates), _ptr(state_delta)))
+
     def setConvVariant(self, variant: int = -1):
         """Force the implicit-GEMM tile shape (-1 = heuristic); process-wide."""
         check(self.lib.tns_set_option(1, int(variant)))
@@ -607,9 +631,15 @@ class TNNHip:
         check(self.lib.tns_set_option(14, int(floats)))
 
     def setConvBf16Tile(self, tile: int = -1):
-        """convForwardBf16's tile: -1 by shape, 0 the 128 x 128 tile, 1 the
+        """convForwardBf16's tile, and convBackwardBf16's for state_delta: -1 by shape, 0 the 128 x 128 tile, 1 the
         64 x 64 one; every tile takes every shape; process-wide."""
         check(self.lib.tns_set_option(15, int(tile)))
+
+    def setConvBf16DwSplit(self, slices: int = -1):
+        """convBackwardBf16's dW: into how many slices its reduction over
+        batch*oh*ow is cut (-1 by shape, v >= 1 that many, clamped to the
+        reduction's steps of 32); process-wide."""
+        check(self.lib.tns_set_option(16, int(slices)))
 
     def setDeriveSums(self, on: bool = False):
         """Conv backward (no batch norm): Derivative fused into addSums'
