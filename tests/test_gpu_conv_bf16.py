@@ -10,12 +10,11 @@ slope <= 1, the same with S / 4 for the logistic.
 import numpy as np
 import pytest
 
+from _conv_bf16_ref import BRANCH_CFG, BRANCH_CONVS, draw, held, reference_forward as reference
 from tensorium_amd import darknet as dn
 from tensorium_amd._abi import ACT
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-U = 2.0 ** -23
 ERR_ARG, ERR_UNSUPPORTED = 1, 4
 
 # C, H, W, filters, k, stride, pad, batch, activation
@@ -29,46 +28,6 @@ CASES = [
 ]
 # the planner's pick, then each tile shape forced: every tile takes every case
 TILES = [-1, 0, 1]
-
-
-def bf16_round(a):
-    """float32 -> nearest-even bf16, as float32 (the upper 16 bits)."""
-    u = np.ascontiguousarray(a, F).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F)
-
-
-def draw(rng, *shape):
-    v = rng.uniform(-1.0, 1.0, shape).astype(F)
-    v[np.abs(v) < 2.0 ** -20] = 0.0
-    return v
-
-
-def reference(torch, x, w, b, k, stride, pad, act):
-    """(ref, bound) of the layer in float64 from the rounded operands."""
-    def conv(a, c):
-        return torch.nn.functional.conv2d(torch.from_numpy(a.astype(np.float64)),
-                                          torch.from_numpy(c.astype(np.float64)),
-                                          stride=stride, padding=pad).numpy()
-    w4 = w.reshape(w.shape[0], x.shape[1], k, k)
-    xr, wr, b8 = bf16_round(x), bf16_round(w4), b.astype(np.float64)[None, :, None, None]
-    y = conv(xr, wr) + b8
-    S = conv(np.abs(xr), np.abs(wr)) + np.abs(b8)
-    if act == ACT["LOGISTIC"]:
-        y, S = 1.0 / (1.0 + np.exp(-y)), S / 4
-    elif act == ACT["LEAKY"]:
-        y = np.where(y < 0, 0.1 * y, y)
-    elif act == ACT["RELU"]:
-        y = np.maximum(y, 0.0)
-    else:
-        assert act == ACT["LINEAR"]
-    return y, (w4[0].size + 2) * U * S + U
-
-
-def held(got, ref, bound, what):
-    err = np.abs(got.astype(np.float64).reshape(ref.shape) - ref)
-    print(what, "max err", err.max(), "max err / bound", (err / bound).max())
-    assert (err <= bound).all(), what
 
 
 @pytest.mark.parametrize("tile", TILES)
@@ -149,3 +108,25 @@ def test_driver(hip, torch_cuda):
         ref, bound = reference(torch, inp, f.weights.reshape(l.filters, -1), f.biases, l.size,
                                l.stride, l.pad, l.activation)
         held(out[l.index].cpu().numpy(), ref, bound, f"layer {l.index}")
+
+
+def test_driver_branches(hip, torch_cuda):
+    """A net with a shortcut, a route of two layers, a maxpool and an upsample
+    between its convs, layer by layer."""
+    torch = torch_cuda
+    net = dn.Network(dn.parse_cfg(BRANCH_CFG))
+    params = dn.random_params(net, seed=21)
+    x = torch.from_numpy(draw(np.random.default_rng(22), 2, 3, 32, 32)).cuda()
+    out = dn.HipDarknet(hip, net, params, torch, precision="bf16").forward(x)
+    hip.finish()
+    convs = [l for l in net.layers if l.kind == "convolutional"]
+    assert [l.index for l in convs] == BRANCH_CONVS
+    assert [net.layers[i].kind for i in (1, 4, 6, 7, 9)] == ["maxpool", "shortcut", "upsample",
+                                                             "route", "yolo"]
+    assert (convs[-1].c, convs[-1].h) == (32, 16)  # the route's two layers, upsampled
+    for l, p in zip(convs, params):
+        f = dn.fuse_batchnorm(l, p)
+        inp = (x if l.index == 0 else out[l.index - 1]).cpu().numpy().reshape(2, l.c, l.h, l.w)
+        ref, bound = reference(torch, inp, f.weights.reshape(l.filters, -1), f.biases, l.size,
+                               l.stride, l.pad, l.activation)
+        print("group driver", held(out[l.index].cpu().numpy(), ref, bound, f"layer {l.index}"))

@@ -9,12 +9,12 @@ values (prior included), n = batch*oh*ow for dW and filters*k*k for dX.
 import numpy as np
 import pytest
 
+from _conv_bf16_ref import (BRANCH_CFG, BRANCH_CONVS, F, draw, held,
+                            reference_backward as reference)
 from tensorium_amd import darknet as dn
 from tensorium_amd._abi import ACT
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-U = 2.0 ** -23
 ERR_ARG, ERR_UNSUPPORTED = 1, 4
 
 # C, H, W, filters, k, stride, pad, batch
@@ -30,49 +30,6 @@ CASES = [
 FORMS = [(-1, -1), (1, -1), (3, -1), (-1, 0), (-1, 1)]
 # ... and one case without state_delta
 RUNS = [(c, s, t, True) for c in CASES for s, t in FORMS] + [(CASES[1], -1, -1, False)]
-
-
-def bf16_round(a):
-    """float32 -> nearest-even bf16, as float32 (the upper 16 bits)."""
-    u = np.ascontiguousarray(a, F).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return u.astype(np.uint32).view(F)
-
-
-def draw(rng, *shape):
-    v = rng.uniform(-1.0, 1.0, shape).astype(F)
-    v[np.abs(v) < 2.0 ** -20] = 0.0
-    return v
-
-
-def reference(torch, x, w, d, k, stride, pad, wu0, sd0):
-    """((ref, bound) of dW, (ref, bound) of dX) in float64 from the rounded
-    operands: x [B, C, H, W], w [filters, C*k*k], d [B, filters, oh, ow], and
-    the buffers' prior contents."""
-    def conv(a, c, **kw):
-        return torch.nn.functional.conv2d(torch.from_numpy(np.ascontiguousarray(a, np.float64)),
-                                          torch.from_numpy(np.ascontiguousarray(c, np.float64)),
-                                          **kw).numpy()
-    (B, C, H, W), (filters, oh, ow) = x.shape, d.shape[1:]
-    xr, dr, wr = bf16_round(x), bf16_round(d), bf16_round(w).reshape(filters, C, k, k)
-    # dW[f, c] = the correlation of x[:, c] with d[:, f], the batch as channels
-    dw = lambda a, c: conv(a.transpose(1, 0, 2, 3), c.transpose(1, 0, 2, 3), padding=pad,  # noqa
-                           dilation=stride)[:, :, :k, :k].transpose(1, 0, 2, 3).reshape(wu0.shape)
-    # dX = d spread by the stride, padded, convolved with the flipped W^T
-    def dx(a, c):
-        up = np.zeros((B, filters, H + k - 1, W + k - 1))
-        up[:, :, k - 1 - pad:, k - 1 - pad:][:, :, :(oh - 1) * stride + 1:stride,
-                                             :(ow - 1) * stride + 1:stride] = a
-        return conv(up, c.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1]).reshape(sd0.shape)
-    SW, SX = dw(np.abs(xr), np.abs(dr)) + np.abs(wu0), dx(np.abs(dr), np.abs(wr)) + np.abs(sd0)
-    return ((dw(xr, dr) + wu0, (B * oh * ow + 2) * U * SW + U),
-            (dx(dr, wr) + sd0, (filters * k * k + 2) * U * SX + U))
-
-
-def held(got, ref, bound, what):
-    err = np.abs(got.astype(np.float64).reshape(ref.shape) - ref)
-    print(what, "max err", err.max(), "max err / bound", (err / bound).max())
-    assert (err <= bound).all(), what
 
 
 _DATA = {}
@@ -229,3 +186,46 @@ def test_train_driver(hip, torch_cuda):
         held(wu, rw.ravel(), bw.ravel(), f"layer {l.index} dW")
         if sd is not None:
             held(sd, rx, bx, f"layer {l.index} dX")
+
+
+def test_train_driver_branches(hip, torch_cuda):
+    """The backward through a net with branches: conv 2's output has three
+    consumers (conv 3, the shortcut, the route), so conv 3's dX adds to a
+    state_delta that is not zero; a maxpool and an upsample lie between convs.
+    Every conv's dW and dX against the reference, the snapshot taken before
+    the layer as dX's prior."""
+    torch = torch_cuda
+    net = dn.Network(dn.parse_cfg(BRANCH_CFG))
+    params = dn.random_params(net, seed=21)
+    tr = dn.HipDarknetTrain(hip, net, params, torch, precision="bf16")
+    rng = np.random.default_rng(22)
+    x = torch.from_numpy(draw(rng, 2, 3, 32, 32)).cuda()
+    tr.forward(x)
+    tr.set_yolo_deltas([torch.from_numpy(draw(rng, tr.delta[9].numel())).cuda()])
+    host = lambda t: t.cpu().numpy().copy()  # noqa: E731
+    before, after = {}, {}
+
+    def snap(l):  # after layer l: what it left, and layer l-1's state_delta before it runs
+        hip.finish()
+        if l.kind == "convolutional":
+            after[l.index] = (host(tr.delta[l.index]), host(tr.conv[l.index]["wu"]),
+                              host(tr.delta[l.index - 1]) if l.index else None)
+        if l.index >= 2:
+            before[l.index - 1] = host(tr.delta[l.index - 2])
+    tr.backward(x, on_backward=snap)
+    convs = [l for l in net.layers if l.kind == "convolutional"]
+    assert [l.index for l in convs] == BRANCH_CONVS
+    # conv 3's input delta: the route's and the shortcut's terms are there before its dX
+    assert np.count_nonzero(before[3]) > before[3].size // 2
+    assert not before[8].any() and not before[2].any()
+    for l in convs:
+        d, wu, sd = after[l.index]
+        inp = host(x if l.index == 0 else tr.out[l.index - 1]).reshape(2, l.c, l.h, l.w)
+        sd0 = before.get(l.index, np.zeros(inp.size, F))
+        (rw, bw), (rx, bx) = reference(torch, inp, host(tr.conv[l.index]["w"]).reshape(l.filters, -1),
+                                       d.reshape(2, l.filters, l.out_h, l.out_w), l.size,
+                                       l.stride, l.pad, np.zeros(wu.shape), sd0)
+        print("group driver", held(wu, rw.ravel(), bw.ravel(), f"layer {l.index} dW"))
+        if sd is not None:
+            assert np.any(sd != sd0)
+            print("group driver", held(sd, rx, bx, f"layer {l.index} dX"))
