@@ -687,6 +687,55 @@ int tns_conv_bf16_backward_bn(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H,
                               const float* variance, float* scale_updates, float* mean_delta,
                               float* variance_delta, float* weight_updates, float* state_delta);
 
+/* ---- bf16 GEMM, the connected / lstm / rnn layers' opt-in reduced precision (gemm_bf16.hip) ----
+ * tns_gemm_bf16: row-major C[M][N] = op(A) . op(B) (+ C) on the bf16 MFMA, on
+ * the context's stream.  A is M x K (transA: K x M), B is K x N (transB:
+ * N x K), fp32 with leading dimensions lda, ldb, ldc, any 4-byte alignment.
+ * Both are rounded to bf16 (nearest even) on their way in; the products (exact
+ * in fp32) are accumulated in fp32.  accumulate = 0 writes C without reading
+ * it; accumulate != 0 adds to it in fp32.  The forms served are NT (transB),
+ * TN (transA) and NN, the connected layer's forward, weight_updates and
+ * state.delta products; TT returns TNS_ERR_UNSUPPORTED.  Not bit-exact against
+ * tns_hip_gemm and not meant to be: with A~, B~ the rounded operands and C0 the
+ * prior C (0 without accumulate), an element lies within
+ *   (K + 2) * 2^-23 * (|op(A~)| . |op(B~)| + |C0|) + 2^-23
+ * of op(A~) . op(B~) + C0, in an accumulation order that is unspecified and
+ * differs between tile shapes and slice counts.  Deterministic: no atomics, the
+ * same call gives the same bits.  Like tns_conv_bf16_* and tns_region_* these
+ * entries are no TNNCuda methods: they join a pending dW of the pipelined conv
+ * backward on every call and stay outside the hazard table.  Scratch (the
+ * slices' partial sums) is the context's.
+ * TNS_ERR_ARG, nothing launched or written: a null operand, a size that is not
+ * positive (or beyond 2^31 - 256), a leading dimension below the row length, a
+ * packed buffer not 16-byte aligned, C overlapping A or B.
+ *
+ * tns_gemm_bf16_packed_bytes: *bytes = the size of the packed form of a weight
+ * matrix [N][K] (rows padded to the k step of 32).
+ * tns_gemm_bf16_pack: one launch; W [N][K] (leading dimension ldw) rounded to
+ * bf16, nearest even, Inf and NaN kept, into packed (16-byte aligned device
+ * memory of tns_gemm_bf16_packed_bytes bytes), zeros in the padding.  The
+ * layout is private to the library.
+ * tns_gemm_bf16_nt_packed: the NT form C[M][N] = A[M][K] . W^T (+ C) with W as
+ * tns_gemm_bf16_pack left it for N x K: no rounding of B, half its bytes; the
+ * inference path, whose weights do not change.  Same bound, same refusals.
+ *
+ * TNS_OPT_GEMM_BF16_TILE (default -1: by shape; v >= 0: tile v, 0 = 64 x 64 on
+ * the 32x32x16 MFMA, 1 = 16 x 128 on the 16x16x32 MFMA, taken where M <= 16)
+ * forces the tile shape; every tile takes every shape.
+ * TNS_OPT_GEMM_BF16_SPLIT (default -1: by shape; v >= 1: v slices, clamped to
+ * the reduction's steps of 32) sets into how many contiguous slices the
+ * reduction over K is cut; their fp32 partial results are added in slice
+ * order, then C's prior value. */
+int tns_gemm_bf16(tns_ctx* ctx, uint8_t transA, uint8_t transB, int64_t M, int64_t N, int64_t K,
+                  const float* A, int64_t lda, const float* B, int64_t ldb, int32_t accumulate,
+                  float* C, int64_t ldc);
+int tns_gemm_bf16_packed_bytes(tns_ctx* ctx, int64_t N, int64_t K, int64_t* bytes);
+int tns_gemm_bf16_pack(tns_ctx* ctx, int64_t N, int64_t K, const float* W, int64_t ldw,
+                       void* packed);
+int tns_gemm_bf16_nt_packed(tns_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A,
+                            int64_t lda, const void* packed, int32_t accumulate, float* C,
+                            int64_t ldc);
+
 /* ---- dropout and the elementwise loss heads (heads.hip) ----
  * tns_hip_dropout_forward = TNNCuda.forwardDropout, the reference's device
  * kernel (cuda_sgemm.cu:1617-1645), a pure function of (seed, i) — the CPU
@@ -1160,7 +1209,8 @@ enum { TNS_OPT_STRICT_BETA0 = 0, TNS_OPT_CONV_VARIANT = 1, TNS_OPT_CONV_PAD = 2,
        TNS_OPT_SDOT_FORM = 6, TNS_OPT_DX_FUSED = 7, TNS_OPT_DX_TILE = 8,
        TNS_OPT_DW_TILE = 9, TNS_OPT_BWD_OVERLAP = 10, TNS_OPT_DX_CONV = 11,
        TNS_OPT_DW_RES = 12, TNS_OPT_DERIVE_SUMS = 13, TNS_OPT_SCRATCH_CAP = 14,
-       TNS_OPT_CONV_BF16_TILE = 15, TNS_OPT_CONV_BF16_DW_SPLIT = 16 };
+       TNS_OPT_CONV_BF16_TILE = 15, TNS_OPT_CONV_BF16_DW_SPLIT = 16,
+       TNS_OPT_GEMM_BF16_TILE = 17, TNS_OPT_GEMM_BF16_SPLIT = 18 };
 int tns_set_option(int32_t opt, int64_t value);
 
 #ifdef __cplusplus

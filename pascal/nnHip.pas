@@ -68,6 +68,8 @@ const
   TNS_OPT_SCRATCH_CAP = 14;
   TNS_OPT_CONV_BF16_TILE = 15;
   TNS_OPT_CONV_BF16_DW_SPLIT = 16;
+  TNS_OPT_GEMM_BF16_TILE = 17;
+  TNS_OPT_GEMM_BF16_SPLIT = 18;
 
 type
   PTnsCtx = pointer;
@@ -274,6 +276,19 @@ function tns_conv_bf16_backward_bn(ctx: PTnsCtx; batch, C, H, W: int64; input, w
   mean, variance, scaleUpdates, meanDelta, varianceDelta, weightUpdates,
   stateDelta: THipMem): longint; cdecl; external libtns;
 
+{ the opt-in bf16 GEMM (gemm_bf16.hip): the connected, lstm and rnn layers' products with
+  the operands rounded to bf16, fp32 accumulation and C; NT, TN and NN; not bit-exact }
+function tns_gemm_bf16(ctx: PTnsCtx; transA, transB: boolean; M, N, K: int64; A: THipMem;
+  lda: int64; B: THipMem; ldb: int64; accumulate: longint; C: THipMem; ldc: int64): longint;
+  cdecl; external libtns;
+function tns_gemm_bf16_packed_bytes(ctx: PTnsCtx; N, K: int64; bytes: PInt64): longint;
+  cdecl; external libtns;
+function tns_gemm_bf16_pack(ctx: PTnsCtx; N, K: int64; W: THipMem; ldw: int64;
+  packedWeights: pointer): longint; cdecl; external libtns;
+function tns_gemm_bf16_nt_packed(ctx: PTnsCtx; M, N, K: int64; A: THipMem; lda: int64;
+  packedWeights: pointer; accumulate: longint; C: THipMem; ldc: int64): longint;
+  cdecl; external libtns;
+
 { dropout (seed in [0, 2^32)) and the elementwise loss heads }
 function tns_hip_dropout_forward(ctx: PTnsCtx; N, seed: int64; probability, scale: single; src,
   rnd, dst: THipMem): longint; cdecl; external libtns;
@@ -456,6 +471,10 @@ type
     procedure convForwardBf16(const batch, C, H, W: SizeInt; const input, packedWeights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
     procedure convBackwardBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta, biasUpdates, weightUpdates, stateDelta: TCUMem);
     procedure convBackwardBNBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta: TCUMem; const scales, x, xNorm, mean, variance: TCUMem; scaleUpdates, meanDelta, varianceDelta, weightUpdates, stateDelta: TCUMem);
+    procedure gemmBf16(const transA, transB: boolean; const M, N, K: SizeInt; const A: TCUMem; const aOffset, lda: SizeInt; const B: TCUMem; const bOffset, ldb: SizeInt; const accumulate: boolean; C: TCUMem; const cOffset, ldc: SizeInt);
+    function gemmBf16PackedBytes(const N, K: SizeInt): SizeInt;
+    procedure gemmBf16Pack(const N, K: SizeInt; const W: TCUMem; const ldw: SizeInt; packedWeights: TCUMem);
+    procedure gemmBf16NTPacked(const M, N, K: SizeInt; const A: TCUMem; const aOffset, lda: SizeInt; const packedWeights: TCUMem; const accumulate: boolean; C: TCUMem; const cOffset, ldc: SizeInt);
     procedure imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64 = nil);
     procedure im2col(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const im: TCUMem; const imOffset: SizeInt; const col: TCUMem; const colOffset: SizeInt);
     procedure col2im(const aChannels, aHeight, aWidth, kernelHeight, kernelWidth, padHeight, padWidth, strideY, strideX, dilationY, dilationX: SizeInt; const col: TCUMem; const colOffset: SizeInt; const im: TCUMem; const imOffset: SizeInt);
@@ -852,6 +871,38 @@ begin
     THipMem(scales), THipMem(x), THipMem(xNorm), THipMem(mean), THipMem(variance),
     THipMem(scaleUpdates), THipMem(meanDelta), THipMem(varianceDelta), THipMem(weightUpdates),
     THipMem(stateDelta)))
+end;
+
+procedure TNNHip<T>.gemmBf16(const transA, transB: boolean; const M, N, K: SizeInt; const A: TCUMem; const aOffset, lda: SizeInt; const B: TCUMem; const bOffset, ldb: SizeInt; const accumulate: boolean; C: TCUMem; const cOffset, ldc: SizeInt);
+begin
+  { gemm's row-major C = op(A) . op(B) (accumulate: + C) on the bf16 MFMA: the
+    operands rounded to bf16 on their way in, singles accumulated and stored;
+    NT, TN and NN; reduced precision, opt-in (the bound is in tns.h) }
+  check(tns_gemm_bf16(FCtx, transA, transB, M, N, K, THipMem(PSingle(A) + aOffset), lda,
+    THipMem(PSingle(B) + bOffset), ldb, ord(accumulate), THipMem(PSingle(C) + cOffset), ldc))
+end;
+
+function TNNHip<T>.gemmBf16PackedBytes(const N, K: SizeInt): SizeInt;
+var
+  bytes: int64;
+begin
+  { bytes of the packed bf16 form of an N x K weight matrix: allocate with
+    createDeviceBuffer(bytes) }
+  check(tns_gemm_bf16_packed_bytes(FCtx, N, K, @bytes));
+  result := bytes
+end;
+
+procedure TNNHip<T>.gemmBf16Pack(const N, K: SizeInt; const W: TCUMem; const ldw: SizeInt; packedWeights: TCUMem);
+begin
+  { a layer's weights [N][K] rounded to bf16 once, for gemmBf16NTPacked }
+  check(tns_gemm_bf16_pack(FCtx, N, K, THipMem(W), ldw, pointer(packedWeights)))
+end;
+
+procedure TNNHip<T>.gemmBf16NTPacked(const M, N, K: SizeInt; const A: TCUMem; const aOffset, lda: SizeInt; const packedWeights: TCUMem; const accumulate: boolean; C: TCUMem; const cOffset, ldc: SizeInt);
+begin
+  { the forward product C = A . W^T of a layer whose weights gemmBf16Pack packed }
+  check(tns_gemm_bf16_nt_packed(FCtx, M, N, K, THipMem(PSingle(A) + aOffset), lda,
+    pointer(packedWeights), ord(accumulate), THipMem(PSingle(C) + cOffset), ldc))
 end;
 
 procedure TNNHip<T>.imageToInput(const count: SizeInt; const src: TCUMem; const isBytes: boolean; const geom: PInt64; const channels, pixelStride: SizeInt; const tableKind: longint; const table: PSingle; const netW, netH: SizeInt; const letter: boolean; dst: TCUMem; const placed: PInt64);

@@ -41,6 +41,8 @@ TNS_OPT_DERIVE_SUMS = 13
 TNS_OPT_SCRATCH_CAP = 14
 TNS_OPT_CONV_BF16_TILE = 15
 TNS_OPT_CONV_BF16_DW_SPLIT = 16
+TNS_OPT_GEMM_BF16_TILE = 17
+TNS_OPT_GEMM_BF16_SPLIT = 18
 
 _CONV = [i64] * 11  # aChannels .. dilationX
 
@@ -270,6 +272,11 @@ PROTOTYPES.update({
     "tns_conv_bf16_backward_bn": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64,
                                             i64, i32, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
                                             fptr, fptr, fptr, fptr, fptr]),
+    # the bf16 GEMM: packed an opaque device buffer, bytes a host int64
+    "tns_gemm_bf16": (C.c_int, [vp, u8, u8, i64, i64, i64, fptr, i64, fptr, i64, i32, fptr, i64]),
+    "tns_gemm_bf16_packed_bytes": (C.c_int, [vp, i64, i64, C.POINTER(i64)]),
+    "tns_gemm_bf16_pack": (C.c_int, [vp, i64, i64, fptr, i64, vp]),
+    "tns_gemm_bf16_nt_packed": (C.c_int, [vp, i64, i64, i64, fptr, i64, vp, i32, fptr, i64]),
     # dropout (the seed an int64 in [0, 2^32)) and the elementwise loss heads
     "tns_hip_dropout_forward": (C.c_int, [vp, i64, i64, f32, f32, fptr, fptr, fptr]),
     "tns_hip_dropout_backward": (C.c_int, [vp, i64, f32, f32, fptr, fptr, fptr]),

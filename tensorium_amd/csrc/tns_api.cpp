@@ -427,6 +427,14 @@ int tns_set_option(int32_t opt, int64_t value) {
     case TNS_OPT_CONV_BF16_DW_SPLIT:
       g_opt.conv_bf16_dw_split = value < 1 ? -1 : value;
       return TNS_OK;
+    case TNS_OPT_GEMM_BF16_TILE:
+      if (value >= gemm_bf16_tile_count())
+        return set_error(TNS_ERR_ARG, "no bf16 gemm tile %lld", (long long)value);
+      g_opt.gemm_bf16_tile = value < 0 ? -1 : value;
+      return TNS_OK;
+    case TNS_OPT_GEMM_BF16_SPLIT:
+      g_opt.gemm_bf16_split = value < 1 ? -1 : value;
+      return TNS_OK;
     default:
       return set_error(TNS_ERR_ARG, "unknown option %d", opt);
   }

@@ -18,7 +18,7 @@ struct tns_ctx {
   bool own_stream = false;
   // device scratch, one buffer per SLOT_* below (im2col workspace, host-API
   // staging, dW partial sums, batch-norm block results, ...)
-  static constexpr int kSlots = 14;
+  static constexpr int kSlots = 15;
   float* scratch[kSlots] = {};
   size_t scratch_elems[kSlots] = {};
   // telemetry (TTensorMetrics-style, nopmetrics.pas:25-44)
@@ -96,12 +96,18 @@ struct Options {
   // TNS_OPT_CONV_BF16_DW_SPLIT: -1 the planner's slice count (conv_bf16_dw_split),
   // v >= 1 that many slices (clamped to the reduction steps)
   int64_t conv_bf16_dw_split = -1;
+  // TNS_OPT_GEMM_BF16_TILE: -1 the planner's tile (gemm_bf16_tile), v >= 0 tile v
+  int64_t gemm_bf16_tile = -1;
+  // TNS_OPT_GEMM_BF16_SPLIT: -1 the planner's slice count (gemm_bf16_split),
+  // v >= 1 that many slices (clamped to the reduction steps)
+  int64_t gemm_bf16_split = -1;
 };
 extern Options g_opt;  // (tns_api.cpp)
 
 enum { SLOT_COL = 0, SLOT_STAGE1 = 1, SLOT_STAGE2 = 2, SLOT_STAGE3 = 3, SLOT_DW = 4, SLOT_BN = 5,
        SLOT_MLP = 6, SLOT_WT = 7, SLOT_COL_DX = 8, SLOT_YOLO = 9, SLOT_RES_A = 10,
-       SLOT_RES_B = 11, SLOT_BF16_WT = 12, SLOT_BF16_DW = 13, SLOT_COUNT = 14 };
+       SLOT_RES_B = 11, SLOT_BF16_WT = 12, SLOT_BF16_DW = 13, SLOT_BF16_GEMM = 14,
+       SLOT_COUNT = 15 };
 static_assert(SLOT_COUNT == tns_ctx::kSlots, "one scratch buffer per slot");
 
 inline int join_side(tns_ctx* c);

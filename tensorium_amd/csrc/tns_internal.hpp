@@ -700,4 +700,33 @@ int64_t conv_bf16_dw_split(int64_t filters, int64_t K, int64_t R, int64_t forced
 hipError_t launch_conv_bf16_dx(int tile, const ConvBf16BwdArgs& c, hipStream_t s);
 hipError_t launch_conv_bf16_dw(int split, const ConvBf16BwdArgs& c, hipStream_t s);
 
+// ---- bf16 GEMM (gemm_bf16.hip) -----------------------------------------------------
+// The connected, lstm and rnn layers' opt-in reduced-precision products:
+// row-major C[M][N] = op(A) . op(B) (+ C), operands rounded to bf16 on their way
+// into LDS, fp32 accumulators and fp32 C.  Tile v of gemm_bf16_tile_count():
+// 0 = 64 x 64, 1 = 16 x 128 (gemm_bf16_tile: by M, or TNS_OPT_GEMM_BF16_TILE);
+// the reduction is cut into gemm_bf16_split slices (by the tile count, or
+// TNS_OPT_GEMM_BF16_SPLIT; the partials [S][M][N] within TNS_OPT_SCRATCH_CAP).
+// Both planners are pure functions.
+enum { GEMM_BF16_NT = 0, GEMM_BF16_TN = 1, GEMM_BF16_NN = 2, GEMM_BF16_NT_PACKED = 3 };
+struct GemmBf16Args {
+  int form;
+  int64_t M, N, K;
+  const float* A;  // NT, NN, NT_PACKED: [M][lda]; TN: [K][lda]
+  int64_t lda;
+  const void* B;   // NT: fp32 [N][ldb]; TN, NN: fp32 [K][ldb]; NT_PACKED: gemm_bf16_pack's
+  int64_t ldb;
+  int accumulate;  // 0: C is written and never read; 1: added to
+  float* C;
+  int64_t ldc;
+  float* part;     // S > 1 slices: S * M * N floats
+};
+int gemm_bf16_tile_count();
+int gemm_bf16_tile(int64_t M, int64_t forced);
+int64_t gemm_bf16_split(int tile, int64_t M, int64_t N, int64_t K, int64_t forced, int64_t cap);
+int64_t gemm_bf16_packed_bytes(int64_t N, int64_t K);
+hipError_t launch_gemm_bf16_pack(int64_t N, int64_t K, const float* W, int64_t ldw, void* packed,
+                                 hipStream_t s);
+hipError_t launch_gemm_bf16(int tile, int split, const GemmBf16Args& g, hipStream_t s);
+
 }  // namespace tns

@@ -20,6 +20,14 @@ and, batch-normalized, ``mean var x xn su md vd`` (one mean / variance pair,
 overwritten each step).  Its attributes ``O`` (outputs), ``I`` (inputs) and
 ``act`` are the layer's own.  Rows are [step][stream]: S rows make one step, n =
 S * O floats one step's slice of ``out`` / ``delta`` / ``x`` / ``xn``.
+
+The state also says which path the layer's three products take
+(``product_nt`` / ``product_tn`` / ``product_nn``, the only place that
+chooses): fp32 ``gemm`` by default; with ``bf16`` set (the drivers'
+``connected_precision="bf16"``) ``gemmBf16``, and ``gemmBf16NTPacked`` for the
+forward when the state holds the packed weights ``wp`` in place of ``w``
+(inference: packed once at construction, the fp32 copy dropped).  Everything
+else stays fp32 on either path.
 """
 from __future__ import annotations
 
@@ -35,11 +43,11 @@ def at(t, off):  # a raw device pointer off floats into t
 class State(dict):
     """The buffers by name, so that iterating it gives tensors only; ``O``,
     ``I`` and ``act`` are attributes, which ``st["O"]`` reads as well."""
-    __slots__ = ("O", "I", "act")
+    __slots__ = ("O", "I", "act", "bf16")
 
-    def __init__(self, O, I, act, **buffers):
+    def __init__(self, O, I, act, bf16=False, **buffers):
         super().__init__(**buffers)
-        self.O, self.I, self.act = O, I, act
+        self.O, self.I, self.act, self.bf16 = O, I, act, bf16
 
     def __missing__(self, key):
         if key in self.__slots__:
@@ -47,13 +55,17 @@ class State(dict):
         raise KeyError(key)
 
 
-def state(t, z, p, O, I, act, bn, rows, training, out=None, delta=None, w=None, wu=None):
+def state(t, z, p, O, I, act, bn, rows, training, out=None, delta=None, w=None, wu=None,
+          hip=None, precision="fp32"):
     """A connected (sub-)layer's device state from its parameter block ``p``.
     ``t`` uploads a NumPy array as float32, ``z(n)`` gives n device zeros;
     ``rows``: steps * streams.  What the owner keeps in buffers of its own is
     passed in: ``out`` / ``delta`` (a layer's output and delta; an lstm side's
-    slab slices), ``w`` / ``wu`` (slab slices; ``w`` takes p's weights)."""
-    st = State(O, I, act, b=t(p.biases), out=z(rows * O) if out is None else out)
+    slab slices), ``w`` / ``wu`` (slab slices; ``w`` takes p's weights).
+    ``precision="bf16"``: the products on the bf16 MFMA; in inference ``hip``
+    packs the weights once and the state keeps ``wp`` instead of ``w``."""
+    st = State(O, I, act, precision == "bf16", b=t(p.biases),
+               out=z(rows * O) if out is None else out)
     if w is None:
         st["w"] = t(p.weights)
     else:
@@ -67,7 +79,44 @@ def state(t, z, p, O, I, act, bn, rows, training, out=None, delta=None, w=None, 
         if bn:
             st.update(mean=z(O), var=z(O), x=z(rows * O), xn=z(rows * O), su=z(O), md=z(O),
                       vd=z(O))
+    elif st.bf16:  # the weights never change: packed once, the fp32 copy dropped
+        st["wp"] = hip.gemmBf16Pack(O, I, st.pop("w"))
     return st
+
+
+def product_nt(hip, st, rows, inp, in_off, out_off):
+    """out[rows][O] (from float out_off) = inp[rows][I] (from in_off) . W^T."""
+    O, I = st.O, st.I
+    if "wp" in st:
+        hip.gemmBf16NTPacked(rows, O, I, inp, in_off, I, st["wp"], False, st["out"], out_off, O)
+    elif st.bf16:
+        hip.gemmBf16(False, True, rows, O, I, inp, in_off, I, st["w"], 0, I, False, st["out"],
+                     out_off, O)
+    else:
+        hip.gemm(False, True, rows, O, I, 1.0, inp, in_off, I, st["w"], 0, I, 0.0, st["out"],
+                 out_off, O)
+
+
+def product_tn(hip, st, rows, d_off, inp, in_off):
+    """weight_updates[O][I] += delta[rows][O] (from d_off)^T . inp[rows][I]."""
+    O, I = st.O, st.I
+    if st.bf16:
+        hip.gemmBf16(True, False, O, I, rows, st["delta"], d_off, O, inp, in_off, I, True,
+                     st["wu"], 0, I)
+    else:
+        hip.gemm(True, False, O, I, rows, 1.0, st["delta"], d_off, O, inp, in_off, I, 1.0,
+                 st["wu"], 0, I)
+
+
+def product_nn(hip, st, rows, d_off, sd, sd_off):
+    """sd[rows][I] (state.delta, from sd_off) += delta[rows][O] (from d_off) . W."""
+    O, I = st.O, st.I
+    if st.bf16:
+        hip.gemmBf16(False, False, rows, I, O, st["delta"], d_off, O, st["w"], 0, I, True, sd,
+                     sd_off, I)
+    else:
+        hip.gemm(False, False, rows, I, O, 1.0, st["delta"], d_off, O, st["w"], 0, I, 1.0, sd,
+                 sd_off, I)
 
 
 def bn_forward(hip, st, S, step, training, activate=True):
@@ -101,9 +150,7 @@ def bn_forward(hip, st, S, step, training, activate=True):
 
 def forward(hip, st, S, step, inp, in_step, training):
     """Step ``step`` from slice ``in_step`` of ``inp`` (S rows of I floats)."""
-    O, I = st.O, st.I
-    hip.gemm(False, True, S, O, I, 1.0, inp, in_step * S * I, I, st["w"], 0, I, 0.0, st["out"],
-             step * S * O, O)
+    product_nt(hip, st, S, inp, in_step * S * st.I, step * S * st.O)
     bn_forward(hip, st, S, step, training)
 
 
@@ -129,12 +176,11 @@ def bn_backward(hip, st, S, step, clamp=True):
 def backward(hip, st, S, step, inp, in_step, sd, sd_step, clamp=True):
     """Step ``step``: weight_updates from slice ``in_step`` of ``inp``, and
     into slice ``sd_step`` of ``sd`` (state.delta) unless it is None."""
-    O, I = st.O, st.I
     bn_backward(hip, st, S, step, clamp)
-    d, off = st["delta"], step * S * O
-    hip.gemm(True, False, O, I, S, 1.0, d, off, O, inp, in_step * S * I, I, 1.0, st["wu"], 0, I)
+    off = step * S * st.O
+    product_tn(hip, st, S, off, inp, in_step * S * st.I)
     if sd is not None:
-        hip.gemm(False, False, S, I, O, 1.0, d, off, O, st["w"], 0, I, 1.0, sd, sd_step * S * I, I)
+        product_nn(hip, st, S, off, sd, sd_step * S * st.I)
 
 
 def update(hip, st, batch, learning_rate, momentum, decay):

@@ -148,11 +148,20 @@ class _Driver(_RnnLayers, _LstmLayers):
     def _z(self, n, dtype=None):
         return self.torch.zeros(n, dtype=dtype, device=self.device)
 
-    def _build(self, hip, net, params, torch, lstm_fused, rnn_fused, training):
+    PRECISIONS = ("fp32", "bf16")
+
+    def _build(self, hip, net, params, torch, lstm_fused, rnn_fused, training,
+               connected_precision="fp32"):
         """Every layer's output (zeros in training, uninitialised in
         inference) and, in training, delta; the lstm, rnn and connected
         layers' states.  Returns the convolutional blocks [(layer, params)],
-        which each driver keeps in its own form."""
+        which each driver keeps in its own form.  ``connected_precision``:
+        the path of every connected layer's and sub-layer's products
+        (``connected.state``)."""
+        if connected_precision not in self.PRECISIONS:
+            raise ValueError(f"connected_precision {connected_precision!r}: one of "
+                             f"{self.PRECISIONS}")
+        self.connected_precision = connected_precision
         self.hip, self.net, self.torch = hip, net, torch
         self.lstm_fused = bool(lstm_fused)
         self.rnn_fused = bool(rnn_fused)
@@ -180,7 +189,8 @@ class _Driver(_RnnLayers, _LstmLayers):
                 self.fc[l.index] = fc.state(self._t, self._z, p, l.filters, l.in_size,
                                             l.activation, l.bn, B, training,
                                             out=self.out[l.index],
-                                            delta=self.delta[l.index] if training else None)
+                                            delta=self.delta[l.index] if training else None,
+                                            hip=hip, precision=connected_precision)
             else:
                 convs.append((l, p))
         return convs
@@ -249,17 +259,25 @@ class HipDarknet(_Driver):
     those layers through ``convForwardBf16``: bf16 operands, fp32
     accumulation, bias, activation and output.  Every other layer, and every
     buffer, is as in fp32; the outputs are close to, not equal to, the fp32
-    path's."""
+    path's.
 
-    PRECISIONS = ("fp32", "bf16")
+    ``connected_precision="bf16"`` (opt-in, likewise; ``precision`` keeps
+    meaning the convolutions only) packs the weights of every connected layer,
+    of an lstm layer's eight and an rnn layer's three sub-layers as bf16 once,
+    drops their fp32 copies and runs their products through
+    ``gemmBf16NTPacked`` (``connected.product_nt``): bf16 operands, fp32
+    accumulation; bias, batch norm, activations and the fused gate kernels
+    stay fp32."""
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch,
-                 lstm_fused: bool = True, rnn_fused: bool = True, precision: str = "fp32"):
+                 lstm_fused: bool = True, rnn_fused: bool = True, precision: str = "fp32",
+                 connected_precision: str = "fp32"):
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision {precision!r}: one of {self.PRECISIONS}")
         self.precision = precision
         self.conv_params = {}
-        for l, p in self._build(hip, net, params, torch, lstm_fused, rnn_fused, training=False):
+        for l, p in self._build(hip, net, params, torch, lstm_fused, rnn_fused, training=False,
+                                connected_precision=connected_precision):
             f = fuse_batchnorm(l, p)
             w = self._t(f.weights)
             if precision == "bf16":  # packed once; the fp32 copy is dropped
@@ -464,16 +482,24 @@ class HipDarknetTrain(_Driver):
     sends every convolutional layer's backward through ``convBackwardBf16`` /
     ``convBackwardBNBf16``: the delta preparation stays fp32, dW and
     state.delta run on the bf16 MFMA with fp32 accumulation into the fp32
-    buffers.  The training forward, the connected and recurrent layers and
-    ``update`` stay fp32 (a bf16 training forward is the follow-up), so only
-    weight_updates and the deltas below a convolution differ from fp32's."""
+    buffers.  The convolutions' training forward and ``update`` stay fp32 (a
+    bf16 training forward is the follow-up), so only weight_updates and the
+    deltas below a convolution differ from fp32's.
+
+    ``connected_precision="bf16"`` (opt-in, likewise; ``precision`` keeps
+    meaning the convolutions only) sends the three products of every
+    connected layer, of an lstm layer's eight and an rnn layer's three
+    sub-layers through ``gemmBf16`` (``connected.product_nt`` / ``_tn`` /
+    ``_nn``): the fp32 weights, inputs and deltas rounded to bf16 on their way
+    in, fp32 accumulation into the fp32 buffers.  Bias, batch norm,
+    activations, the fused gate kernels and ``update`` stay fp32."""
 
     LOSS_KINDS = ("softmax", "cost", "logistic")
-    PRECISIONS = HipDarknet.PRECISIONS
 
     def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
                  seed: int = 0, lstm_fused: bool = True, rnn_fused: bool = True,
-                 yolo_loss: bool = False, precision: str = "fp32"):
+                 yolo_loss: bool = False, precision: str = "fp32",
+                 connected_precision: str = "fp32"):
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision {precision!r}: one of {self.PRECISIONS}")
         self.precision = precision
@@ -492,7 +518,8 @@ class HipDarknetTrain(_Driver):
                 raise ValueError("yolo_loss=True: the [yolo] layers disagree on max: "
                                  f"{[l.max_boxes for l in yolos]} (one truth tensor feeds all)")
         self.rng = np.random.default_rng(seed)  # default dropout seeds
-        convs = self._build(hip, net, params, torch, lstm_fused, rnn_fused, training=True)
+        convs = self._build(hip, net, params, torch, lstm_fused, rnn_fused, training=True,
+                            connected_precision=connected_precision)
         B, z, t = net.batch, self._z, self._t
         self.rnd = {l.index: z(B * l.out_size) for l in net.layers if l.kind == "dropout"}
         # softmax / logistic: loss[batch*inputs]; every loss layer: cost[1]

@@ -62,7 +62,10 @@ class _LstmLayers:
                     L["sub"][g] = fc.state(self._t, z, p, O, K, b.activation, l.bn, T * S, training,
                                            out=cut("_out", T * n), w=cut("_w", O * K),
                                            delta=cut("_delta", T * n) if training else None,
-                                           wu=cut("_wu", O * K) if training else None)
+                                           wu=cut("_wu", O * K) if training else None,
+                                           hip=self.hip, precision=self.connected_precision)
+                if "wp" in L["sub"][names[0]]:  # packed: the fp32 slab is dropped
+                    del L[side + "_w"]
             self.lstm[l.index] = L
 
     def reset_state(self):
@@ -105,8 +108,13 @@ class _LstmLayers:
             return
         # the input-side products of every step and gate at once: an NT
         # product's element is one sdot of an input row and a weight row
-        hip.gemmStridedBatched(False, True, T * S, O, I, 1.0, inp, 0, I, 0, L["u_w"], 0, I, O * I,
-                               0.0, L["u_out"], 0, O, T * n, 4)
+        # (on the bf16 path one product a gate: connected.py chooses the call)
+        if sub["uf"].bf16:
+            for g in self.U:
+                fc.product_nt(hip, sub[g], T * S, inp, 0, 0)
+        else:
+            hip.gemmStridedBatched(False, True, T * S, O, I, 1.0, inp, 0, I, 0, L["u_w"], 0, I,
+                                   O * I, 0.0, L["u_out"], 0, O, T * n, 4)
         for g in self.U:
             if l.bn:  # statistics are per step
                 for i in range(T):
@@ -115,8 +123,12 @@ class _LstmLayers:
                 hip.forwardBias(T * n, sub[g]["out"], 0, O, sub[g]["b"], 1, T * S)
         for i in range(T):
             off = i * n
-            hip.gemmStridedBatched(False, True, S, O, O, 1.0, L["h"], 0, O, 0, L["w_w"], 0, O,
-                                   O * O, 0.0, L["w_out"], off, O, T * n, 4)
+            if sub["wf"].bf16:
+                for g in self.W:
+                    fc.product_nt(hip, sub[g], S, L["h"], 0, off)
+            else:
+                hip.gemmStridedBatched(False, True, S, O, O, 1.0, L["h"], 0, O, 0, L["w_w"], 0, O,
+                                       O * O, 0.0, L["w_out"], off, O, T * n, 4)
             for g in self.W:
                 fc.bn_forward(hip, sub[g], S, i, training)
             hip.lstmGatesForward(n, [at(sub[g]["out"], off) for g in self.W],
@@ -184,18 +196,22 @@ class _LstmLayers:
             for g in LSTM_GATES:
                 fc.bn_backward(hip, sub[g], S, i, False)
             # the dW products: four outputs each, one operand shared
-            hip.gemmStridedBatched(True, False, O, O, S, 1.0, L["w_delta"], off, O, T * n, hprev,
-                                   hoff, O, 0, 1.0, L["w_wu"], 0, O, O * O, 4)
-            hip.gemmStridedBatched(True, False, O, I, S, 1.0, L["u_delta"], off, O, T * n, inp,
-                                   i * S * I, I, 0, 1.0, L["u_wu"], 0, I, O * I, 4)
+            if sub["wf"].bf16:
+                for g in self.W:
+                    fc.product_tn(hip, sub[g], S, off, hprev, hoff)
+                for g in self.U:
+                    fc.product_tn(hip, sub[g], S, off, inp, i * S * I)
+            else:
+                hip.gemmStridedBatched(True, False, O, O, S, 1.0, L["w_delta"], off, O, T * n,
+                                       hprev, hoff, O, 0, 1.0, L["w_wu"], 0, O, O * O, 4)
+                hip.gemmStridedBatched(True, False, O, I, S, 1.0, L["u_delta"], off, O, T * n, inp,
+                                       i * S * I, I, 0, 1.0, L["u_wu"], 0, I, O * I, 4)
             if i:  # into the layer's own delta, slice i-1, in the reference's order
                 for g in ("wo", "wg", "wi", "wf"):
-                    hip.gemm(False, False, S, O, O, 1.0, sub[g]["delta"], off, O, sub[g]["w"], 0, O,
-                             1.0, delta, off - n, O)
+                    fc.product_nn(hip, sub[g], S, off, delta, off - n)
         if sd is not None:  # slice i of the layer below's delta takes step i's four products
             for g in ("uo", "ug", "ui", "uf"):
-                hip.gemm(False, False, T * S, I, O, 1.0, sub[g]["delta"], 0, O, sub[g]["w"], 0, I,
-                         1.0, sd, 0, I)
+                fc.product_nn(hip, sub[g], T * S, 0, sd, 0)
         hip.copy(n, cell, 0, 1, L["c"], 0, 1)
         hip.copy(n, out, 0, 1, L["h"], 0, 1)
 
@@ -239,7 +255,8 @@ class _RnnLayers:
                 own = g == "output"  # the layer's own buffers
                 L["sub"][g] = fc.state(self._t, z, p, b.filters, b.in_size, b.activation, l.bn,
                                        T * S, training, out=self.out[l.index] if own else None,
-                                       delta=self.delta[l.index] if own and training else None)
+                                       delta=self.delta[l.index] if own and training else None,
+                                       hip=self.hip, precision=self.connected_precision)
             self.rnn[l.index] = L
 
     def reset_state(self):
@@ -277,14 +294,13 @@ class _RnnLayers:
             return
         # the input sub-layer's products of every step at once: an NT product's
         # element is one sdot of an input row and a weight row
-        hip.gemm(False, True, T * S, H, I, 1.0, inp, 0, I, si["w"], 0, I, 0.0, si["out"], 0, H)
+        fc.product_nt(hip, si, T * S, inp, 0, 0)
         if l.bn and not training:  # by the rolling statistics: per element, any grouping
             hip.normalize(H, T * n, T * S, si["rm"], 1, si["rv"], 1, si["out"], 0)
             hip.forwardScaleAdd(T * n, si["out"], 0, H, si["scales"], si["b"], 1, T * S)
         for i in range(T):
             off = i * n
-            hip.gemm(False, True, S, H, H, 1.0, state, off, H, ss["w"], 0, H, 0.0, ss["out"], off,
-                     H)
+            fc.product_nt(hip, ss, S, state, off, off)
             if l.bn:  # training: the statistics are per step
                 if training:
                     fc.bn_forward(hip, si, S, i, True, activate=False)
@@ -295,8 +311,7 @@ class _RnnLayers:
         # the output sub-layer after the loop: step i reads state[i + j0], which
         # step i alone writes and no later step changes (in inference the steps
         # of one call do not chain: step i + 1 reads state[i + 1], not this one)
-        hip.gemm(False, True, T * S, O, H, 1.0, state, j0 * n, H, so["w"], 0, H, 0.0, so["out"], 0,
-                 O)
+        fc.product_nt(hip, so, T * S, state, j0 * n, 0)
         if not l.bn:
             hip.forwardBias(T * m, so["out"], 0, O, so["b"], 1, T * S)
         elif training:
@@ -341,8 +356,7 @@ class _RnnLayers:
         if not fused:
             return
         if sd is not None:  # slice i of the layer below's delta takes step i's product alone
-            hip.gemm(False, False, T * S, I, H, 1.0, si["delta"], 0, H, si["w"], 0, I, 1.0, sd, 0,
-                     I)
+            fc.product_nn(hip, si, T * S, 0, sd, 0)
         if l.bn and T > 1:
             # the reference clamps the whole delta at every step: a slice that
             # normalizeDelta pushed outside [-1, 1] is clamped by the next step

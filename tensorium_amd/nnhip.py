@@ -551,6 +551,51 @@ class TNNHip:
             _ptr(mean), _ptr(variance), _ptr(scale_updates), _ptr(mean_delta),
             _ptr(variance_delta), _ptr(weight_updates), _ptr(state_delta)))
 
+    # the connected / lstm / rnn layers' opt-in reduced precision (tns_gemm_bf16*): not bit-exact
+    def gemmBf16(self, transA, transB, M, N, K, A, aOffset, lda, B, bOffset, ldb, accumulate, C_,
+                 cOffset, ldc):
+        """gemm's row-major C = op(A) . op(B) (accumulate: + C) on the bf16
+        MFMA: fp32 operands (element offsets as in gemm) rounded to bf16 on
+        their way in, fp32 accumulation and C.  NT, TN and NN."""
+        check(self.lib.tns_gemm_bf16(self.ctx, int(bool(transA)), int(bool(transB)), M, N, K,
+                                     _ptr(A) + 4 * aOffset, lda, _ptr(B) + 4 * bOffset, ldb,
+                                     int(bool(accumulate)), _ptr(C_) + 4 * cOffset, ldc))
+
+    def gemmBf16PackedBytes(self, N, K) -> int:
+        """Bytes of the packed bf16 form of a weight matrix [N][K]."""
+        n = C.c_int64(0)
+        check(self.lib.tns_gemm_bf16_packed_bytes(self.ctx, N, K, C.byref(n)))
+        return int(n.value)
+
+    def gemmBf16Pack(self, N, K, W, wOffset=0, ldw=None, packed=None):
+        """W [N][K] (device float32, leading dimension ldw, K by default)
+        rounded to bf16 into the library's packed layout.  packed: a uint8
+        device tensor of gemmBf16PackedBytes(N, K) bytes or a raw pointer;
+        allocated when None.  Returns packed."""
+        if packed is None:
+            packed = torch.empty(self.gemmBf16PackedBytes(N, K), dtype=torch.uint8,
+                                 device=W.device)
+        check(self.lib.tns_gemm_bf16_pack(self.ctx, N, K, _ptr(W) + 4 * wOffset,
+                                          K if ldw is None else ldw, _bptr(packed)))
+        return packed
+
+    def gemmBf16NTPacked(self, M, N, K, A, aOffset, lda, packed, accumulate, C_, cOffset, ldc):
+        """C[M][N] = A[M][K] . W^T (accumulate: + C) with W as gemmBf16Pack
+        left it: the inference form, no rounding of W and half its bytes."""
+        check(self.lib.tns_gemm_bf16_nt_packed(self.ctx, M, N, K, _ptr(A) + 4 * aOffset, lda,
+                                               _bptr(packed), int(bool(accumulate)),
+                                               _ptr(C_) + 4 * cOffset, ldc))
+
+    def setGemmBf16Tile(self, tile: int = -1):
+        """gemmBf16's tile: -1 by shape, 0 the 64 x 64 tile, 1 the 16 x 128
+        one; every tile takes every shape; process-wide."""
+        check(self.lib.tns_set_option(17, int(tile)))
+
+    def setGemmBf16Split(self, slices: int = -1):
+        """gemmBf16: into how many slices the reduction over K is cut (-1 by
+        shape, v >= 1 that many, clamped to its steps of 32); process-wide."""
+        check(self.lib.tns_set_option(18, int(slices)))
+
     def setConvVariant(self, variant: int = -1):
         """Force the implicit-GEMM tile shape (-1 = heuristic); process-wide."""
         check(self.lib.tns_set_option(1, int(variant)))
