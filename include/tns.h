@@ -651,6 +651,43 @@ int tns_conv_bf16_forward(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int
                           int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
                           int32_t activation, float* out);
 
+/* ---- bf16 convolution training forward, opt-in (conv_bf16_train.hip) ----
+ * The same product on the bf16 MFMA from the plain fp32 weights
+ * [filters][C*kSize*kSize] (row-major, k in the (c, ky, kx) order, any 4-byte
+ * alignment) that tns_hip_sgd_update just wrote: they are rounded to bf16
+ * (nearest even, Inf and NaN kept) on their way into the kernel, with no packed
+ * copy, no pre-pass and no scratch.  One launch; no atomics, the same call
+ * gives the same bits, and for the same tile shape the bits of
+ * tns_conv_bf16_pack + tns_conv_bf16_forward.
+ *
+ * tns_conv_bf16_forward_weights: tns_conv_bf16_forward with weights in place
+ * of packed: the same bound, TNS_OPT_CONV_BF16_TILE and refusals (weights null
+ * instead of packed null or misaligned; out overlapping input or weights).
+ *
+ * tns_conv_bf16_forward_train: operands and meaning of
+ * tns_hip_conv_forward_train at dilation 1, without a workspace.  The product
+ * is stored raw into out: it lies within (K + 2) * 2^-23 * conv(|w~|, |x~|) +
+ * 2^-23 of the exact convolution of the rounded operands.  Everything after it
+ * is tns_hip_conv_forward_train's own fp32 chain on that product, bit for bit:
+ * MeansAndVars, the rolling update, x := out, normalize, x_norm := out, scale,
+ * bias, activate; with training == 0 the normalization by the rolling
+ * statistics (mean, variance, x, x_norm not touched, may be NULL).  The batch
+ * statistics are not gathered in the product's epilogue, so that the chain
+ * stays the fp32 one.  TNS_ERR_ARG, nothing launched or written, in addition
+ * to tns_conv_bf16_forward_weights': a null batch-norm operand; out, x or
+ * x_norm overlapping input or weights. */
+int tns_conv_bf16_forward_weights(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int64_t W,
+                                  const float* input, const float* weights, const float* biases,
+                                  int64_t filters, int64_t kSize, int64_t stride,
+                                  int64_t padding, int32_t activation, float* out);
+int tns_conv_bf16_forward_train(tns_ctx* ctx, int64_t batch, int64_t C, int64_t H, int64_t W,
+                                const float* input, const float* weights, int64_t filters,
+                                int64_t kSize, int64_t stride, int64_t padding,
+                                int32_t activation, const float* scales, const float* biases,
+                                float* rolling_mean, float* rolling_variance, float bnMomentum,
+                                int32_t training, float* mean, float* variance, float* x,
+                                float* x_norm, float* out);
+
 /* ---- bf16 convolution backward, opt-in reduced-precision training (conv_bf16_bwd.hip) ----
  * tns_conv_bf16_backward[_bn]: operands and meaning of tns_hip_conv_backward[_bn]
  * at dilation 1, without a workspace.  The delta preparation (Derivative, then

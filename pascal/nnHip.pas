@@ -266,6 +266,17 @@ function tns_conv_bf16_pack(ctx: PTnsCtx; filters, K: int64; weights: THipMem;
 function tns_conv_bf16_forward(ctx: PTnsCtx; batch, C, H, W: int64; input: THipMem;
   packedWeights: pointer; biases: THipMem; filters, kSize, stride, padding: int64;
   activation: longint; output: THipMem): longint; cdecl; external libtns;
+{ the opt-in bf16 convolution training forward (conv_bf16_train.hip): the same product from
+  the plain single weights, rounded inside the kernel; _train: tns_hip_conv_forward_train at
+  dilation 1 without a workspace, its batch-norm chain unchanged }
+function tns_conv_bf16_forward_weights(ctx: PTnsCtx; batch, C, H, W: int64; input, weights,
+  biases: THipMem; filters, kSize, stride, padding: int64; activation: longint;
+  output: THipMem): longint; cdecl; external libtns;
+function tns_conv_bf16_forward_train(ctx: PTnsCtx; batch, C, H, W: int64; input,
+  weights: THipMem; filters, kSize, stride, padding: int64; activation: longint;
+  scales, biases, rolling_mean, rolling_variance: THipMem; bnMomentum: single;
+  training: longint; mean, variance, x, x_norm, output: THipMem): longint;
+  cdecl; external libtns;
 { the opt-in bf16 convolution backward (conv_bf16_bwd.hip): tns_hip_conv_backward[_bn] at
   dilation 1 with dW and state.delta on the bf16 MFMA; plain single weights, no workspace }
 function tns_conv_bf16_backward(ctx: PTnsCtx; batch, C, H, W: int64; input, weights: THipMem;
@@ -469,6 +480,8 @@ type
     function convBf16PackedBytes(const filters, K: SizeInt): SizeInt;
     procedure convBf16Pack(const filters, K: SizeInt; const weights: TCUMem; packedWeights: TCUMem);
     procedure convForwardBf16(const batch, C, H, W: SizeInt; const input, packedWeights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
+    procedure convForwardBf16Weights(const batch, C, H, W: SizeInt; const input, weights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
+    procedure convForwardTrainBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const scales, biases: TCUMem; rollingMean, rollingVariance: TCUMem; const bnMomentum: single; const training: boolean; mean, variance, x, xNorm, output: TCUMem);
     procedure convBackwardBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta, biasUpdates, weightUpdates, stateDelta: TCUMem);
     procedure convBackwardBNBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta: TCUMem; const scales, x, xNorm, mean, variance: TCUMem; scaleUpdates, meanDelta, varianceDelta, weightUpdates, stateDelta: TCUMem);
     procedure gemmBf16(const transA, transB: boolean; const M, N, K: SizeInt; const A: TCUMem; const aOffset, lda: SizeInt; const B: TCUMem; const bOffset, ldb: SizeInt; const accumulate: boolean; C: TCUMem; const cOffset, ldc: SizeInt);
@@ -851,6 +864,24 @@ begin
     the bf16 MFMA: reduced precision, opt-in; input and output stay singles }
   check(tns_conv_bf16_forward(FCtx, batch, C, H, W, THipMem(input), pointer(packedWeights),
     THipMem(biases), filters, kSize, stride, padding, activation, THipMem(output)))
+end;
+
+procedure TNNHip<T>.convForwardBf16Weights(const batch, C, H, W: SizeInt; const input, weights, biases: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; output: TCUMem);
+begin
+  { convForwardBf16 from the layer's plain single weights, rounded inside the
+    kernel: the training forward of a layer without batch norm, nothing packed }
+  check(tns_conv_bf16_forward_weights(FCtx, batch, C, H, W, THipMem(input), THipMem(weights),
+    THipMem(biases), filters, kSize, stride, padding, activation, THipMem(output)))
+end;
+
+procedure TNNHip<T>.convForwardTrainBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const scales, biases: TCUMem; rollingMean, rollingVariance: TCUMem; const bnMomentum: single; const training: boolean; mean, variance, x, xNorm, output: TCUMem);
+begin
+  { the batch-normalized layer's training forward (dilation 1) with the product
+    on the bf16 MFMA; the batch-norm chain after it is convForwardTrain's own }
+  check(tns_conv_bf16_forward_train(FCtx, batch, C, H, W, THipMem(input), THipMem(weights),
+    filters, kSize, stride, padding, activation, THipMem(scales), THipMem(biases),
+    THipMem(rollingMean), THipMem(rollingVariance), bnMomentum, ord(training), THipMem(mean),
+    THipMem(variance), THipMem(x), THipMem(xNorm), THipMem(output)))
 end;
 
 procedure TNNHip<T>.convBackwardBf16(const batch, C, H, W: SizeInt; const input, weights: TCUMem; const filters, kSize, stride, padding: SizeInt; const activation: longint; const output: TCUMem; delta, biasUpdates, weightUpdates, stateDelta: TCUMem);

@@ -266,6 +266,13 @@ PROTOTYPES.update({
     "tns_conv_bf16_pack": (C.c_int, [vp, i64, i64, fptr, vp]),
     "tns_conv_bf16_forward": (C.c_int, [vp, i64, i64, i64, i64, fptr, vp, fptr, i64, i64, i64,
                                         i64, i32, fptr]),
+    # the bf16 conv training forward: plain fp32 weights; tns_hip_conv_forward_train without
+    # dilation and workspace
+    "tns_conv_bf16_forward_weights": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, fptr, i64, i64,
+                                                i64, i64, i32, fptr]),
+    "tns_conv_bf16_forward_train": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64,
+                                              i64, i32, fptr, fptr, fptr, fptr, f32, i32, fptr,
+                                              fptr, fptr, fptr, fptr]),
     # the bf16 conv backward: tns_hip_conv_backward[_bn] without dilation and workspace
     "tns_conv_bf16_backward": (C.c_int, [vp, i64, i64, i64, i64, fptr, fptr, i64, i64, i64, i64,
                                          i32, fptr, fptr, fptr, fptr, fptr]),

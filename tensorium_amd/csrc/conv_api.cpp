@@ -569,6 +569,35 @@ int exec_conv_forward(tns_ctx* c, const ConvFwdPlan& p, const ConvFwdOps& o) {
   }
 }
 
+// The batch-norm chain of a training forward on the product in out
+// (nbaselayer.pas:336-370): MeansAndVars, the rolling update, x := out,
+// normalize, x_norm := out, scale, bias, activate; without training,
+// blockNormalize with the rolling statistics instead
+int run_conv_bn(tns_ctx* c, int64_t batch, int64_t filters, int64_t bs, int32_t activation,
+                const float* scales, const float* biases, float* rolling_mean,
+                float* rolling_variance, float bnMomentum, int32_t training, float* mean,
+                float* variance, float* x, float* x_norm, int srss_quirk, float* out) {
+  OpTimer t(c, TNS_OP_BIAS);
+  if (!training)
+    return hip_status(launch_bn_apply(out, nullptr, nullptr, out, batch, filters, bs,
+                                      rolling_mean, rolling_variance, scales, biases, activation,
+                                      c->stream),
+                      "batchNorm launch");
+  float* part;
+  if (int r = ensure_scratch(c, SLOT_BN, 2 * batch * filters, &part)) return r;
+  if (int r = hip_status(launch_means_vars(out, batch, filters, bs, mean, variance, srss_quirk,
+                                           part, c->stream),
+                         "meansAndVars launch"))
+    return r;
+  if (int r = hip_status(launch_rolling_update(filters, rolling_mean, rolling_variance, mean,
+                                               variance, bnMomentum, c->stream),
+                         "rolling update launch"))
+    return r;
+  return hip_status(launch_bn_apply(out, x, x_norm, out, batch, filters, bs, mean, variance,
+                                    scales, biases, activation, c->stream),
+                    "batchNorm launch");
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace
 
@@ -609,25 +638,9 @@ int tns_hip_conv_forward_train(tns_ctx* c, int64_t batch, int64_t C, int64_t H, 
   const ConvFwdPlan p = plan_conv_forward(s, TNS_CONV_FUSED, false, g_opt);
   if (int r = exec_conv_forward(c, p, ConvFwdOps{input, weights, nullptr, workspace, out}))
     return r;
-  OpTimer t(c, TNS_OP_BIAS);
-  if (!training)  // blockNormalize with the rolling statistics, scale, bias, activate
-    return hip_status(launch_bn_apply(out, nullptr, nullptr, out, batch, filters, bs,
-                                      rolling_mean, rolling_variance, scales, biases, activation,
-                                      c->stream),
-                      "batchNorm launch");
-  float* part;
-  if (int r = ensure_scratch(c, SLOT_BN, 2 * batch * filters, &part)) return r;
-  if (int r = hip_status(launch_means_vars(out, batch, filters, bs, mean, variance, p.srss_quirk,
-                                           part, c->stream),
-                         "meansAndVars launch"))
-    return r;
-  if (int r = hip_status(launch_rolling_update(filters, rolling_mean, rolling_variance, mean,
-                                               variance, bnMomentum, c->stream),
-                         "rolling update launch"))
-    return r;
-  return hip_status(launch_bn_apply(out, x, x_norm, out, batch, filters, bs, mean, variance,
-                                    scales, biases, activation, c->stream),
-                    "batchNorm launch");
+  return run_conv_bn(c, batch, filters, bs, activation, scales, biases, rolling_mean,
+                     rolling_variance, bnMomentum, training, mean, variance, x, x_norm,
+                     p.srss_quirk, out);
 }
 
 // ---- backward ------------------------------------------------------------------
@@ -1079,34 +1092,62 @@ int tns_conv_bf16_pack(tns_ctx* c, int64_t filters, int64_t K, const float* weig
                     "conv bf16 pack");
 }
 
+namespace {
+bool meet(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// what every bf16 forward entry refuses of a layer's sizes; the output plane
+int bf16_forward_shape(const char* me, int64_t batch, int64_t C, int64_t H, int64_t W,
+                       int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
+                       int32_t activation, int64_t* oh, int64_t* ow) {
+  if (!act_supported(activation))
+    return set_error(TNS_ERR_UNSUPPORTED, "%s: activation %d not implemented", me, activation);
+  if (batch <= 0 || C <= 0 || H <= 0 || W <= 0 || filters <= 0 || kSize <= 0 || stride <= 0 ||
+      padding < 0)
+    return set_error(TNS_ERR_ARG, "%s: a size is not positive", me);
+  // the k-table's tap displacements and its sentinels (16384) must fall
+  // outside every window; offsets inside one image are 32-bit
+  if (H + padding >= 0x4000 || W + padding >= 0x4000 || kSize >= 0x4000 || stride >= 0x4000 ||
+      C > 0x0fffffffLL || C * H * W * 4 > 0x7fffffffLL || batch > 0x7fffffffLL)
+    return set_error(TNS_ERR_ARG, "%s: image, padding or kernel too large", me);
+  if (int r = bf16_matrix(me, filters, C * kSize * kSize)) return r;
+  *oh = out_dim(H, padding, kSize, 1, stride);
+  *ow = out_dim(W, padding, kSize, 1, stride);
+  if (*oh <= 0 || *ow <= 0)
+    return set_error(TNS_ERR_ARG, "%s: the kernel exceeds the padded image", me);
+  if (filters * *oh * *ow > 0x7fffffffLL)
+    return set_error(TNS_ERR_ARG, "%s: an output image beyond 2^31 elements", me);
+  return TNS_OK;
+}
+
+// the product from the plain fp32 weights (conv_bf16_train.hip); biases null: raw
+int run_bf16_weights(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
+                     const float* input, const float* weights, const float* biases,
+                     int64_t filters, int64_t kSize, int64_t stride, int64_t padding, int64_t oh,
+                     int64_t ow, int32_t activation, float* out, const char* what) {
+  const int tile = conv_bf16_pick(filters, batch * oh * ow, g_opt.conv_bf16_tile);
+  ConvBf16Args v{};
+  if (int r = get_ktab(c, C, H, W, kSize, kSize, 1, 1, &v.ktab)) return r;
+  v.input = input, v.bias = biases, v.out = out;
+  v.batch = batch, v.C = C, v.H = H, v.W = W, v.filters = filters, v.ks = kSize;
+  v.stride = stride, v.pad = padding, v.oh = oh, v.ow = ow, v.act = activation;
+  OpTimer t(c, TNS_OP_GEMM);
+  return hip_status(launch_conv_bf16_weights(tile, v, weights, c->stream), what);
+}
+}  // namespace
+
 int tns_conv_bf16_forward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
                           const float* input, const void* packed, const float* biases,
                           int64_t filters, int64_t kSize, int64_t stride, int64_t padding,
                           int32_t activation, float* out) {
   if (int r = check_ctx(c)) return r;
-  if (!act_supported(activation))
-    return set_error(TNS_ERR_UNSUPPORTED, "conv bf16 forward: activation %d not implemented",
-                     activation);
-  if (batch <= 0 || C <= 0 || H <= 0 || W <= 0 || filters <= 0 || kSize <= 0 || stride <= 0 ||
-      padding < 0)
-    return set_error(TNS_ERR_ARG, "conv bf16 forward: a size is not positive");
-  // the k-table's tap displacements and its sentinels (16384) must fall
-  // outside every window; offsets inside one image are 32-bit
-  if (H + padding >= 0x4000 || W + padding >= 0x4000 || kSize >= 0x4000 || stride >= 0x4000 ||
-      C > 0x0fffffffLL || C * H * W * 4 > 0x7fffffffLL || batch > 0x7fffffffLL)
-    return set_error(TNS_ERR_ARG, "conv bf16 forward: image, padding or kernel too large");
-  if (int r = bf16_matrix("conv bf16 forward", filters, C * kSize * kSize)) return r;
-  const int64_t oh = out_dim(H, padding, kSize, 1, stride);
-  const int64_t ow = out_dim(W, padding, kSize, 1, stride);
-  if (oh <= 0 || ow <= 0)
-    return set_error(TNS_ERR_ARG, "conv bf16 forward: the kernel exceeds the padded image");
-  if (filters * oh * ow > 0x7fffffffLL)
-    return set_error(TNS_ERR_ARG, "conv bf16 forward: an output image beyond 2^31 elements");
+  int64_t oh, ow;
+  if (int r = bf16_forward_shape("conv bf16 forward", batch, C, H, W, filters, kSize, stride,
+                                 padding, activation, &oh, &ow))
+    return r;
   if (!input || !packed || !biases || !out || !aligned16(packed))
     return set_error(TNS_ERR_ARG,
                      "conv bf16 forward: null operand, or packed not 16-byte aligned");
-  const Span a = span(input, batch * C * H * W), b = span(out, batch * filters * oh * ow);
-  if (a.lo < b.hi && b.lo < a.hi)
+  if (meet(span(input, batch * C * H * W), span(out, batch * filters * oh * ow)))
     return set_error(TNS_ERR_ARG, "conv bf16 forward: input and out overlap");
   const int tile = conv_bf16_pick(filters, batch * oh * ow, g_opt.conv_bf16_tile);
   ConvBf16Args v{};
@@ -1118,13 +1159,67 @@ int tns_conv_bf16_forward(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64
   return hip_status(launch_conv_bf16(tile, v, c->stream), "conv bf16 forward");
 }
 
+// ---- bf16 convolution training forward (conv_bf16_train.hip) -----------------------
+// The same product from the plain fp32 [filters][K] weights, rounded on their
+// way into LDS: no packed copy.  _train: the raw product, then
+// tns_hip_conv_forward_train's own fp32 batch-norm chain (run_conv_bn)
+int tns_conv_bf16_forward_weights(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
+                                  const float* input, const float* weights, const float* biases,
+                                  int64_t filters, int64_t kSize, int64_t stride,
+                                  int64_t padding, int32_t activation, float* out) {
+  const char* const me = "conv bf16 forward_weights";
+  if (int r = check_ctx(c)) return r;
+  int64_t oh, ow;
+  if (int r = bf16_forward_shape(me, batch, C, H, W, filters, kSize, stride, padding, activation,
+                                 &oh, &ow))
+    return r;
+  if (!input || !weights || !biases || !out) return set_error(TNS_ERR_ARG, "%s: null operand", me);
+  const Span so = span(out, batch * filters * oh * ow);
+  if (meet(span(input, batch * C * H * W), so) || meet(span(weights, filters * C * kSize * kSize), so))
+    return set_error(TNS_ERR_ARG, "%s: out overlaps input or weights", me);
+  return run_bf16_weights(c, batch, C, H, W, input, weights, biases, filters, kSize, stride,
+                          padding, oh, ow, activation, out, me);
+}
+
+int tns_conv_bf16_forward_train(tns_ctx* c, int64_t batch, int64_t C, int64_t H, int64_t W,
+                                const float* input, const float* weights, int64_t filters,
+                                int64_t kSize, int64_t stride, int64_t padding,
+                                int32_t activation, const float* scales, const float* biases,
+                                float* rolling_mean, float* rolling_variance, float bnMomentum,
+                                int32_t training, float* mean, float* variance, float* x,
+                                float* x_norm, float* out) {
+  const char* const me = "conv bf16 forward_train";
+  if (int r = check_ctx(c)) return r;
+  int64_t oh, ow;
+  if (int r = bf16_forward_shape(me, batch, C, H, W, filters, kSize, stride, padding, activation,
+                                 &oh, &ow))
+    return r;
+  if (!input || !weights || !out) return set_error(TNS_ERR_ARG, "%s: null operand", me);
+  if (!scales || !biases || !rolling_mean || !rolling_variance ||
+      (training && (!mean || !variance || !x || !x_norm)))
+    return set_error(TNS_ERR_ARG, "%s: null batch-norm operand", me);
+  const int64_t n = batch * filters * oh * ow;
+  const Span si = span(input, batch * C * H * W), sw = span(weights, filters * C * kSize * kSize);
+  const auto reads = [&](const float* p) { return meet(si, span(p, n)) || meet(sw, span(p, n)); };
+  if (reads(out) || (training && (reads(x) || reads(x_norm))))
+    return set_error(TNS_ERR_ARG, "%s: out, x or x_norm overlaps input or weights", me);
+  // the chain's scratch before the launch that writes out
+  float* part;
+  if (training)
+    if (int r = ensure_scratch(c, SLOT_BN, 2 * batch * filters, &part)) return r;
+  if (int r = run_bf16_weights(c, batch, C, H, W, input, weights, nullptr, filters, kSize, stride,
+                               padding, oh, ow, activation, out, me))
+    return r;
+  return run_conv_bn(c, batch, filters, oh * ow, activation, scales, biases, rolling_mean,
+                     rolling_variance, bnMomentum, training, mean, variance, x, x_norm,
+                     (int)g_opt.srss_quirk, out);
+}
+
 // ---- bf16 convolution backward (conv_bf16_bwd.hip) ---------------------------------
 // Opt-in reduced-precision training: the fp32 delta preparation of
 // tns_hip_conv_backward[_bn] (run_bwd_prologue), then dW and dX on the bf16
 // MFMA, all on the context's stream
 namespace {
-bool meet(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
 int conv_bf16_backward(tns_ctx* c, const ConvShape& s, const ConvBwdOps& o) {
   const char* const me = "conv bf16 backward";
   if (!c) return check_ctx(c);

@@ -1,6 +1,7 @@
 // conv_bf16_common.hpp — what the bf16 MFMA convolution kernels share
-// (conv_bf16.hip, conv_bf16_bwd.hip): the vector types, the LDS row geometry,
-// the float -> bf16 rounding and the 16-byte LDS store of rounded pairs.
+// (conv_bf16.hip, conv_bf16_bwd.hip, conv_bf16_train.hip): the vector types,
+// the LDS row geometry, the float -> bf16 rounding and the 16-byte LDS store of
+// rounded pairs.
 // Device code only; include it inside the file's no-packed-fp32-ops region.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +29,12 @@ __device__ __forceinline__ unsigned bf16_rne(float f) {
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
+// two floats rounded into one bf16 pair, lo in the low half (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ unsigned bf16_pair(float lo, float hi) {
+  const f32x2 p = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
+}
+
 // KPT consecutive k of one row, rounded (v_cvt_pk_bf16_f32), as 16-byte pieces
 template <int KPT>
 __device__ __forceinline__ void store_b(unsigned char* row, const float (&g)[KPT]) {
@@ -35,10 +42,7 @@ __device__ __forceinline__ void store_b(unsigned char* row, const float (&g)[KPT
   for (int q = 0; q < KPT / 8; ++q) {
     unsigned w[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2 p = {g[8 * q + 2 * j], g[8 * q + 2 * j + 1]};
-      w[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
-    }
+    for (int j = 0; j < 4; ++j) w[j] = bf16_pair(g[8 * q + 2 * j], g[8 * q + 2 * j + 1]);
     reinterpret_cast<uint4*>(row)[q] = make_uint4(w[0], w[1], w[2], w[3]);
   }
 }

@@ -673,6 +673,11 @@ int64_t conv_bf16_packed_bytes(int64_t filters, int64_t K);
 hipError_t launch_conv_bf16_pack(int64_t filters, int64_t K, const float* weights, void* packed,
                                  hipStream_t s);
 hipError_t launch_conv_bf16(int tile, const ConvBf16Args& c, hipStream_t s);
+// The same product from the plain fp32 weights [filters][C*ks*ks], rounded on
+// their way into LDS (conv_bf16_train.hip): c.packed is not read; c.bias null
+// stores the raw accumulators, else bias and activation as launch_conv_bf16
+hipError_t launch_conv_bf16_weights(int tile, const ConvBf16Args& c, const float* weights,
+                                    hipStream_t s);
 
 // ---- bf16 conv backward (conv_bf16_bwd.hip) --------------------------------------
 // The opt-in reduced-precision training path: dW and dX of a layer on the bf16

@@ -482,9 +482,15 @@ class HipDarknetTrain(_Driver):
     sends every convolutional layer's backward through ``convBackwardBf16`` /
     ``convBackwardBNBf16``: the delta preparation stays fp32, dW and
     state.delta run on the bf16 MFMA with fp32 accumulation into the fp32
-    buffers.  The convolutions' training forward and ``update`` stay fp32 (a
-    bf16 training forward is the follow-up), so only weight_updates and the
-    deltas below a convolution differ from fp32's.
+    buffers.  ``update`` stays fp32, and so does the convolutions' training
+    forward unless ``forward_precision`` says otherwise.
+
+    ``forward_precision="bf16"`` (opt-in, independent of ``precision``, which
+    keeps meaning the backward) sends every convolutional layer's training
+    forward through ``convForwardTrainBf16`` (batch norm) or
+    ``convForwardBf16Weights`` (the others): the product on the bf16 MFMA from
+    the fp32 master weights ``update`` wrote, rounded inside the kernel, fp32
+    accumulation; the batch-norm chain after it is ``convForwardTrain``'s own.
 
     ``connected_precision="bf16"`` (opt-in, likewise; ``precision`` keeps
     meaning the convolutions only) sends the three products of every
@@ -499,10 +505,14 @@ class HipDarknetTrain(_Driver):
     def __init__(self, hip, net: Network, params: list[ConvParams], torch, loss_scale: float = 1.0,
                  seed: int = 0, lstm_fused: bool = True, rnn_fused: bool = True,
                  yolo_loss: bool = False, precision: str = "fp32",
-                 connected_precision: str = "fp32"):
+                 connected_precision: str = "fp32", forward_precision: str = "fp32"):
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision {precision!r}: one of {self.PRECISIONS}")
+        if forward_precision not in self.PRECISIONS:
+            raise ValueError(f"forward_precision {forward_precision!r}: one of "
+                             f"{self.PRECISIONS}")
         self.precision = precision
+        self.forward_precision = forward_precision
         self.loss_scale = float(loss_scale)
         self.yolo_loss = bool(yolo_loss)
         yolos = net.yolos()
@@ -608,7 +618,16 @@ class HipDarknetTrain(_Driver):
             out = self.out[l.index]
             if l.kind == "convolutional":
                 st = self.conv[l.index]
-                if l.bn:
+                if self.forward_precision == "bf16" and l.bn:
+                    hip.convForwardTrainBf16(B, l.c, l.h, l.w, prev, st["w"], l.filters, l.size,
+                                             l.stride, l.pad, l.activation, st["scales"],
+                                             st["b"], st["rm"], st["rv"], 0.1, True, st["mean"],
+                                             st["var"], st["x"], st["xn"], out)
+                elif self.forward_precision == "bf16":
+                    hip.convForwardBf16Weights(B, l.c, l.h, l.w, prev, st["w"], st["b"],
+                                               l.filters, l.size, l.stride, l.pad, l.activation,
+                                               out)
+                elif l.bn:
                     hip.convForwardTrain(B, l.c, l.h, l.w, prev, st["w"], l.filters, l.size,
                                          l.stride, l.pad, 1, l.activation, st["scales"], st["b"],
                                          st["rm"], st["rv"], 0.1, True, st["mean"], st["var"],

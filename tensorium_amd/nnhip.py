@@ -497,6 +497,27 @@ class TNNHip:
                                              _ptr(biases), filters, kSize, stride, padding,
                                              int(activation), _ptr(out)))
 
+    # the opt-in reduced-precision training forward (conv_bf16_train.hip): not bit-exact
+    def convForwardBf16Weights(self, batch, C_, H, W, input, weights, biases, filters, kSize,
+                               stride, padding, activation, out):
+        """convForwardBf16 from the plain fp32 weights [filters][C*k*k], rounded
+        to bf16 inside the kernel: nothing packed."""
+        check(self.lib.tns_conv_bf16_forward_weights(
+            self.ctx, batch, C_, H, W, _ptr(input), _ptr(weights), _ptr(biases), filters, kSize,
+            stride, padding, int(activation), _ptr(out)))
+
+    def convForwardTrainBf16(self, batch, C_, H, W, input, weights, filters, kSize, stride,
+                             padding, activation, scales, biases, rolling_mean, rolling_variance,
+                             bnMomentum, training, mean, variance, x, x_norm, out):
+        """convForwardTrain at dilation 1 with the product on the bf16 MFMA
+        (fp32 weights rounded inside the kernel); the batch-norm chain after it
+        is convForwardTrain's own, fp32."""
+        check(self.lib.tns_conv_bf16_forward_train(
+            self.ctx, batch, C_, H, W, _ptr(input), _ptr(weights), filters, kSize, stride, padding,
+            int(activation), _ptr(scales), _ptr(biases), _ptr(rolling_mean),
+            _ptr(rolling_variance), float(bnMomentum), int(bool(training)), _ptr(mean),
+            _ptr(variance), _ptr(x), _ptr(x_norm), _ptr(out)))
+
     def convBackward(self, batch, C_, H, W, input, weights, filters, kSize, stride, padding,
                      dilation, activation, output, delta, bias_updates, weight_updates,
                      workspace=None, state_delta=None):
